@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: decoded information Gbit/s, BG1 Z=384 (K=8448) R=1/3, 25 iterations.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds every leg beyond the headline, each
+outside the timed region: the parity-stop leg (early_term), and at N = 1 the host-path leg (e2e) and the CPU baselines
+(cpu_baseline); with more than one rank the strong-scaled BASELINE configs[4] leg (cfg5_strong).  --dump-outputs DIR
+writes what the last timed step delivered to the caller (a seeded sample of its hard decisions, float32) to DIR.
 
 A "step" is one pass of the hot path (the decode kernel behind nrldpc_decode_dev, i.e. the
 replacement of step(hLDPCDecoder, cw_tilde) at NRLDPCDecoder.m:265) over one batch of 4096 synthetic
@@ -149,6 +154,20 @@ def synth_llr(torch, codec, batch, seed, dev):
     llr[:, 2 * Z + E_TX:] = 0.0
     torch.cuda.synchronize()
     return info, llr.to(torch.float16).contiguous()
+
+
+DUMP_ROWS, DUMP_SEED = 1024, 0xD0  # --dump-outputs: 1024 of the batch's codewords, 1024 x 8448 float32 = 34.6 MB
+
+
+def dump_outputs(torch, out_dir, hard):
+    """--dump-outputs: what the timed path handed its caller in the last step -- the hard decisions nrldpc_decode_dev wrote (the
+    iteration counts and a-posteriori values are not requested by the timed call) -- as float32 0/1 in DIR/hard_decisions.npy.
+    Of a batch larger than DUMP_ROWS a fixed sample: the rows np.random.default_rng(DUMP_SEED) draws, in ascending order."""
+    batch = hard.shape[0]
+    rows = np.arange(batch) if batch <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(batch, DUMP_ROWS, replace=False))
+    sample = hard[torch.from_numpy(rows).to(hard.device)].cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "hard_decisions.npy"), sample)
 
 
 CFG5_TOTAL, CFG5_LAYERS, CFG5_E, CFG5_ESN0 = 65536, 5, 9478, 7.5  # BASELINE.json configs[4]: BG1 Z=384 R=8/9, early termination
@@ -493,9 +512,9 @@ def dry_run(args, torch):
         time.sleep(0.001 * (rank + 1))
     comm.barrier()
     elapsed = comm.max(time.perf_counter() - t0)
-    # the per-GPU bookkeeping of the cfg5_strong leg: a few numbers per rank
+    # the per-GPU bookkeeping of the cfg5_strong leg (--full or --cfg5): a few numbers per rank
     leg = None
-    if world > 1:
+    if world > 1 and (args.full or args.cfg5):
         lo, hi = importlib.import_module("ldpc-3gpp-matlab_amd.shard").shard_range(args.cfg5_total, rank, world)
         comm.barrier()
         t0 = time.perf_counter()
@@ -670,6 +689,8 @@ def in_process(args, torch, nrldpc):
         pool.decode_dev(d_llr, counts, d_hard)  # returns when every shard's stream is idle
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # shard 0's hard decisions (the seeds of the launcher form's rank 0)
+        dump_outputs(torch, args.dump_outputs, hards[0])
     # event-pair kernel times: of the last timed call per shard, plus a second, untimed pass that reads them after every call
     kms_rows = []
     for _ in range(args.steps):
@@ -693,10 +714,14 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=BATCH, help="codewords per GPU per step")
-    ap.add_argument("--cpu-sample", type=int, default=1024, help="codewords for the all-core CPU baselines (0 = skip)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive host-path leg")
-    ap.add_argument("--no-early-term", action="store_true", help="skip the extra early_term leg (reference semantics)")
-    ap.add_argument("--cfg5", action="store_true", help="also run the cfg5_strong leg at N = 1 (it always runs with more than one rank)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline, outside the timed region: early_term, "
+                    "and at N = 1 the host-path leg and the CPU baselines; with more than one rank cfg5_strong")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (a seeded sample of "
+                    "its hard decisions, float32) to DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=1024, help="codewords for the all-core CPU baselines under --full (0 = skip)")
+    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive host-path leg of --full")
+    ap.add_argument("--no-early-term", action="store_true", help="skip the early_term leg of --full (reference semantics)")
+    ap.add_argument("--cfg5", action="store_true", help="also run the cfg5_strong leg, at any N (--full runs it with more than one rank)")
     ap.add_argument("--cfg5-total", type=int, default=CFG5_TOTAL, help="codewords in the WHOLE job of the cfg5_strong leg")
     ap.add_argument("--cfg5-steps", type=int, default=5, help="timed passes of the cfg5_strong leg")
     ap.add_argument("--backend", default="nccl", help="what carries the barrier / max-time of a multi-rank job: nccl (= RCCL; probed, "
@@ -768,15 +793,17 @@ def main():
     elapsed = comm.max(time.perf_counter() - t0)
     kms = [e0.elapsed_time(e1) for e0, e1 in ev]
     kernel_ms = float(np.mean(kms))
+    if rank == 0 and args.dump_outputs:  # rank 0's hard decisions: its seed is that of the one-rank run
+        dump_outputs(torch, args.dump_outputs, hard)
 
     bler = float((hard != info).any(dim=1).float().mean().item())
     # every rank's kernel time, for the per-GPU roofline fractions of the line (bookkeeping: one number per rank)
     kms_all = [r[0] for r in comm.gather([kernel_ms])]
 
-    # Extra leg, outside the timed region: the reference's own mode -- 'Parity check satisfied' (NRLDPCDecoder.m:120) --
+    # --full, outside the timed region: the reference's own mode -- 'Parity check satisfied' (NRLDPCDecoder.m:120) --
     # on the same LLRs (rank 0 only; never `value`, whose workload is the fixed-25 configuration BASELINE.json names)
     early = None
-    if rank == 0 and not args.no_early_term:
+    if args.full and rank == 0 and not args.no_early_term:
         c_et = nrldpc.Codec(BG, Z, max_iter=ITERS, n_layers=0, early_term=True, llr_dtype=np.float16, device_id=local_rank)
         its = torch.empty(batch, device=dev, dtype=torch.int32)
         hard_et = torch.empty_like(hard)
@@ -793,12 +820,12 @@ def main():
 
     # BASELINE configs[4], strong-scaled over the ranks of the job (every rank takes part: it has a barrier of its own)
     cfg5 = None
-    if world > 1 or args.cfg5:
+    if (args.full and world > 1) or args.cfg5:
         cfg5 = cfg5_strong_leg(torch, nrldpc, comm, args, world, rank, local_rank, dev, valu_insts_per_edge_iteration(nrldpc, batch))
 
     if rank == 0:
         out = build_line(nrldpc, args, world, batch, elapsed, kms, kms_all, rule, bler, early, cfg5, comm.info)
-        if world == 1:  # CPU baseline and host-path legs at N = 1 only
+        if args.full and world == 1:  # CPU baseline and host-path legs: --full at N = 1 only
             # the host-path leg first: the all-core CPU baselines spend the process's CPU quota (the MI355X boxes grant 16
             # CPUs of the 256 they show) and a throttled process measures the throttle, not the path
             if not args.no_e2e:

@@ -88,7 +88,7 @@ def test_bench_rank_protocol_runs_under_gloo():
     import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--backend", "gloo", "--dry-run"]
+           "--backend", "gloo", "--dry-run", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stdout + p.stderr
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -108,7 +108,7 @@ def test_bench_starts_its_own_ranks_and_refuses_a_wrong_rank_count():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo",
-                        "--dry-run"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+                        "--dry-run", "--full"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stdout + p.stderr
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -129,8 +129,8 @@ def test_bench_falls_back_to_gloo_when_rccl_does_not_come_up():
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"],
-                       capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)  # no --backend: the driver's form
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run",
+                        "--full"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)  # no --backend: the driver's form
     assert p.returncode == 0, p.stdout + p.stderr
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -148,3 +148,18 @@ def test_in_process_form_is_refused_under_a_launcher():
     q = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--in-process"], capture_output=True, text=True,
                        timeout=120, cwd=ROOT, env=env)
     assert q.returncode != 0 and "--in-process" in q.stderr and "{" not in q.stdout
+
+
+def test_plain_bench_runs_the_headline_only():
+    """A plain `bench.py --gpus N` times the headline and nothing else: the strong-scaled leg of BASELINE configs[4] runs only under
+    --full (or --cfg5), here with two ranks under gloo through the dry run's protocol."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo",
+                        "--dry-run"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert p.returncode == 0, p.stdout + p.stderr
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["ms_per_step"] >= 2.0 and rec["cfg5_strong"] is None

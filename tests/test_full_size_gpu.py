@@ -326,7 +326,7 @@ def test_bench_two_ranks_sharing_one_gpu():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--batch", "1024", "--backend", "gloo", "--share-gpu", "--cfg5-total", "4096", "--cfg5-steps", "2"]
+           "--batch", "1024", "--backend", "gloo", "--share-gpu", "--full", "--cfg5-total", "4096", "--cfg5-steps", "2"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -343,7 +343,7 @@ def test_bench_two_ranks_sharing_one_gpu():
     # ... and launched PLAINLY: `python bench.py --gpus 2` starts its two ranks itself
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "512",
-                        "--backend", "gloo", "--share-gpu", "--cfg5-total", "2048", "--cfg5-steps", "1"],
+                        "--backend", "gloo", "--share-gpu", "--full", "--cfg5-total", "2048", "--cfg5-steps", "1"],
                        capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -371,7 +371,7 @@ def test_bench_survives_an_rccl_that_does_not_come_up_and_has_a_one_process_rout
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "512",
-                        "--share-gpu", "--cfg5-total", "2048", "--cfg5-steps", "1"],
+                        "--share-gpu", "--full", "--cfg5-total", "2048", "--cfg5-steps", "1"],
                        capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

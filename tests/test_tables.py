@@ -1,8 +1,6 @@
-"""Base-graph tables: structural invariants of TS 38.212 Tables 5.3.2-1/-2/-3 and, where the
-reference checkout exists (build container only), entry-by-entry equality with
-get_3gpp_base_graph.m / get_3gpp_valid_lifting_sizes.m."""
+"""Base-graph tables: structural invariants of TS 38.212 Tables 5.3.2-1/-2/-3 and entry-by-entry equality with
+get_3gpp_base_graph.m (its two tables stored as tests/golden/base_graph_tables.npz) / get_3gpp_valid_lifting_sizes.m."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,7 +13,7 @@ BG2_DEG = [8, 10, 8, 10, 4, 6, 6, 6, 4, 5, 5, 5, 4, 5, 5, 4, 5, 5, 4, 4, 4, 4, 3
            4, 4, 3, 4, 4, 4, 4]
 BG1_MAX = [255, 383, 319, 223, 283, 351, 207, 237]
 BG2_MAX = [254, 190, 158, 222, 143, 175, 205, 239]
-REF = "/root/reference/get_3gpp_base_graph.m"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "base_graph_tables.npz")
 
 
 def _raw(orc, bg, ils):
@@ -63,14 +61,11 @@ def test_max_shift_per_set(orc, bg, mx):
         assert s.max() == mx[ils] % zmax or s.max() == mx[ils]
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present (GPU box)")
 def test_equals_reference_file(orc):
-    txt = open(REF).read()
-    tabs = re.findall(r"table\{(\d)\}\s*=\s*\[(.*?)\];", txt, re.S)
-    assert len(tabs) == 2
-    for bg_s, body in tabs:
-        bg = int(bg_s)
-        rows = np.array([[int(t) for t in ln.split()] for ln in body.strip().splitlines() if ln.strip()])
+    tabs = np.load(REF)  # get_3gpp_base_graph.m's table{1}, table{2} (tests/golden/make_base_graph_tables.py)
+    assert sorted(tabs.files) == ["bg1", "bg2"]
+    for bg in (1, 2):
+        rows = tabs["bg%d" % bg].astype(np.int64)
         assert rows.shape[1] == 10
         for ils in range(8):
             for z in (zz for zz in ALL_Z if orc.set_index(zz) == ils):

@@ -1,4 +1,4 @@
-"""testbench.m as data: the random parameter draws of /root/reference/testbench.m:21-36 and a SECOND, function-style
+"""testbench.m as data: the random parameter draws of the reference's testbench.m:21-36 and a SECOND, function-style
 transcription of the parameter chain NRLDPC.m:297-543 + validatePropertiesImpl (:551-559) + the lifting-size / set-index
 helpers -- written straight from the .m text, sharing no code with ldpc-3gpp-matlab_amd/nrldpc.py (the class-style mirror
 the product uses), so that an error in either shows up as a disagreement.  Test infrastructure only."""

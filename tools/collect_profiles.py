@@ -5,6 +5,9 @@ import json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+if tag == "--results-dir":  # the folder this script reads: tools/final_session.sh writes its bench lines there
+    print(G)
+    sys.exit(0)
 pairs = [("bench_line.json", "_bench_line.json"), ("bench_configs.json", "_bench_configs.json"), ("bench_all_z.json", "_bench_all_z.json"),
          ("bench_chain.json", "_bench_chain.json"), ("bench_montecarlo.json", "_bench_montecarlo.json"),
          ("bench_host_path.json", "_bench_host_path.json"), ("bler_gap.json", "_bler_gap.json"),
