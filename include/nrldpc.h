@@ -139,6 +139,35 @@ int nrldpc_get_dims(nrldpc_handle h, nrldpc_dims* out);
  * handle created with that n_layers gives.  NRLDPC_ERR_UNSUPPORTED for any other value.
  * (A System object's rate is tunable between step() calls -- G, rv_id: NRLDPC.m:51-85 -- so the count is too.) */
 int nrldpc_set_layers(nrldpc_handle h, int32_t n_layers);
+/* Decoding algorithm of the calls that follow (every decode entry point of the handle, nrldpc_decode_multi_dev and the pool
+ * paths included).  No device work.  These entry points were added without a revision bump (NRLDPC_ABI_VERSION stays 6,
+ * nrldpc_cfg keeps its size): a binding detects them by symbol.
+ *   NRLDPC_ALG_MIN_SUM (default): the layered offset-normalised min-sum kernels on the int8 grid, unchanged.
+ *   NRLDPC_ALG_SUM_PRODUCT: flooding sum-product with the parity-check stop -- the reference's comm.LDPCDecoder
+ *     (NRLDPCDecoder.m:120) -- with the semantics of orc_decode_bp_flood_app in oracle/nrldpc_oracle.c, computed in fp32:
+ *     - ingest: f32 / f16 as given, host f64 narrowed to f32; NOT quantised (no int8 grid, no llr_scale, no clamp); NaN -> 0,
+ *       +inf kept (filler bits).  cfg.alpha, cfg.beta and cfg.llr_scale are not read.  Host-pointer calls never take the
+ *       int8 route of large batches (nrldpc_quantise_llr); they send the caller's format.
+ *     - messages r (check to variable) start at 0; a sweep: APP = lambda + sum r; q = APP - r_old (an infinite APP stays
+ *       infinite); r_new = 2 atanh(prod over the other edges of tanh(q/2)) with the product clamped to +-(1 - 1e-15), i.e.
+ *       |r| <= 35.23; every q of a sweep from the same APP (flooding); APP recomputed from r_new.
+ *     - stop: early_term = 1 after the first sweep in which every ACTIVE check holds on APP < 0 (the count reported is that
+ *       sweep's number); early_term = 0 exactly max_iter sweeps; early_term = 2 is refused (NRLDPC_ERR_UNSUPPORTED, here and
+ *       by nrldpc_set_algorithm on such a handle).  Active layers ("Active layers" above) leave rows out as the oracle's
+ *       n_layers does; NRLDPC_LAYERS_AUTO finds the count as for min-sum.
+ *     - app_out: the a-posteriori LLRs after the last sweep.  Results are bit-identical from run to run and independent of the
+ *       batch, its split and its neighbours (no atomics; one fixed order of operations per codeword).
+ *     - tolerance against orc_decode_bp_flood_app (double): |APP - APP_ref| <= 1e-3 * max(1, |APP_ref|) on every finite entry,
+ *       infinite entries equal, signs equal wherever |APP_ref| > 1e-3.  Measured on an MI355X over BG1 / BG2, 13 lifting sizes
+ *       (2 ... 384), all / 4 / an intermediate layer count, 1..3 sweeps at Es/N0 = -3 dB with punctured and filler columns
+ *       (234 cases, 1.04e7 entries; tests/test_sum_product_gpu.py): at most 2.9e-6 absolute, 1.6e-6 relative to max(1, |APP_ref|).
+ *       The check node runs in the phi domain (phi(x) = -ln tanh(x/2)) with prefix and suffix sums, so fp32 reaches the
+ *       oracle's cap; DESIGN.md section 4.10 holds the derivation.
+ * NRLDPC_ERR_UNSUPPORTED for any other value. */
+#define NRLDPC_ALG_MIN_SUM 0     /* default: the layered offset-normalised min-sum kernels (unchanged) */
+#define NRLDPC_ALG_SUM_PRODUCT 1 /* flooding sum-product, the reference's comm.LDPCDecoder (NRLDPCDecoder.m:120) */
+int nrldpc_set_algorithm(nrldpc_handle h, int32_t algorithm);
+int nrldpc_get_algorithm(nrldpc_handle h, int32_t* algorithm);
 /* LLR element type of the calls that follow (NRLDPC_LLR_*; NRLDPC_LLR_F64 for host pointers only): a gateway whose caller holds
  * `single` or `double` arrays hands each over as it is, through one handle (staging buffers grow on demand). */
 int nrldpc_set_llr_dtype(nrldpc_handle h, int32_t llr_dtype);
@@ -182,7 +211,8 @@ int nrldpc_quantise_llr(int8_t* dst, const void* src, int64_t n, int32_t llr_dty
  * non-null.  Results are those of n nrldpc_decode_dev calls.  The launch tables go through a ring of four
  * (pinned, device, event) slots owned by h[0], so calls in flight on different streams never share one; asynchronous on
  * `stream`.  (The reference decodes one code block per step(), NRLDPCDecoder.m:257-266; a receiver serving many
- * users holds exactly such a mix of (BG, Z_c).) */
+ * users holds exactly such a mix of (BG, Z_c).)  A handle set to NRLDPC_ALG_SUM_PRODUCT is decoded by a launch of its own on
+ * `stream` -- the result of nrldpc_decode_dev -- while the min-sum handles of the call keep their shared launches. */
 int nrldpc_decode_multi_dev(int32_t n, const nrldpc_handle* h, const void* const* d_llr, const int32_t* batch,
                             uint8_t* const* d_hard, int32_t* const* d_iters, void* stream);
 
@@ -202,6 +232,8 @@ int nrldpc_pool_decode_packed(nrldpc_pool_handle p, const void* llr, int32_t bat
  * batch (host form: before the chunks are dealt; device form: every shard scans its slice, the maximum is taken, then every
  * shard launches), so the result does not depend on how the batch is cut. */
 int nrldpc_pool_set_layers(nrldpc_pool_handle p, int32_t n_layers);
+/* nrldpc_set_algorithm for every handle of the pool (added without a revision bump, as nrldpc_set_algorithm) */
+int nrldpc_pool_set_algorithm(nrldpc_pool_handle p, int32_t algorithm);
 /* The same for data that is already ON the devices: shard i (entry i of device_ids) decodes batch[i] codewords from
  * d_llr[i] into d_hard[i] (and d_iters[i] when d_iters and d_iters[i] are non-null); every pointer of shard i is
  * device memory of device_ids[i], in cfg.llr_dtype (F32 / F16).  One host thread per shard launches on the shard's

@@ -27,6 +27,22 @@ class NRLDPCError(RuntimeError):
 
 ABI_VERSION = 6  # NRLDPC_ABI_VERSION of include/nrldpc.h
 LAYERS_ALL, LAYERS_AUTO = 0, -1  # NRLDPC_LAYERS_*
+# NRLDPC_ALG_*: the layered offset-normalised min-sum kernels (default), or flooding sum-product -- the reference's
+# comm.LDPCDecoder (NRLDPCDecoder.m:120) -- selected per handle by nrldpc_set_algorithm
+ALG_MIN_SUM, ALG_SUM_PRODUCT = 0, 1
+ALGORITHMS = {"min-sum": ALG_MIN_SUM, "sum-product": ALG_SUM_PRODUCT}
+
+
+def algorithm_code(algorithm):
+    """NRLDPC_ALG_* of an algorithm name ("min-sum" / "sum-product"); UnsupportedParameters for anything else (no device call)."""
+    try:
+        return ALGORITHMS[algorithm]
+    except (KeyError, TypeError):
+        raise UnsupportedParameters("unknown decoding algorithm %r (one of %s)" % (algorithm, ", ".join(ALGORITHMS))) from None
+
+
+def algorithm_name(code):
+    return {v: k for k, v in ALGORITHMS.items()}[int(code)]
 
 
 class Cfg(C.Structure):
@@ -76,7 +92,8 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_version", "nrldpc_build_id", "nrldpc_kernel_id", "nrldpc_pool_create", "nrldpc_pool_decode", "nrldpc_pool_last_split",
            "nrldpc_pool_destroy", "nrldpc_pool_decode_dev", "nrldpc_pool_size", "nrldpc_abi_version", "nrldpc_decode_packed",
            "nrldpc_set_layers", "nrldpc_set_llr_dtype", "nrldpc_last_layers", "nrldpc_count_layers", "nrldpc_pool_set_layers", "nrldpc_pool_decode_packed",
-           "nrldpc_decode_packed_layers", "nrldpc_pool_set_timing", "nrldpc_pool_last_kernel_ms", "nrldpc_last_host_phases", "nrldpc_payload_bits_dev"]
+           "nrldpc_decode_packed_layers", "nrldpc_pool_set_timing", "nrldpc_pool_last_kernel_ms", "nrldpc_last_host_phases", "nrldpc_payload_bits_dev",
+           "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm"]
 
 _lib = None
 
@@ -152,6 +169,9 @@ def load():
     L.nrldpc_pool_set_layers.argtypes = [vp, i32]
     L.nrldpc_set_layers.argtypes = [vp, i32]
     L.nrldpc_set_llr_dtype.argtypes = [vp, i32]
+    L.nrldpc_set_algorithm.argtypes = [vp, i32]
+    L.nrldpc_get_algorithm.argtypes = [vp, C.POINTER(i32)]
+    L.nrldpc_pool_set_algorithm.argtypes = [vp, i32]
     L.nrldpc_last_layers.argtypes = [vp, C.POINTER(i32)]
     L.nrldpc_count_layers.argtypes = [i32, i32, vp, i32, i32]
     L.nrldpc_pool_last_split.argtypes = [vp, C.POINTER(i32)]
@@ -197,11 +217,14 @@ class Codec:
     comm.LDPCDecoder / comm.LDPCEncoder in the reference (NRLDPCDecoder.m:120, NRLDPCEncoder.m:49)."""
 
     def __init__(self, bg, Z, max_iter=50, n_layers=0, early_term=True, alpha=0.0, llr_scale=0,
-                 llr_dtype=np.float32, device_id=0, max_batch=0, beta=0.0, crc=None):
+                 llr_dtype=np.float32, device_id=0, max_batch=0, beta=0.0, crc=None, algorithm="min-sum"):
         """alpha = 0: the library picks the check-node rule (alpha, beta) by rate (nrldpc_default_rule);
         otherwise message magnitude = max(alpha*min - beta, 0), beta in LLR units.
         n_layers: 0 = every row, 4..rows, or LAYERS_AUTO (-1) = read off each call's LLRs; set_layers() changes it between calls.
-        crc = (poly with its x^L term, L, K'): the CRC-aided stop (nrldpc_cfg.early_term = 2) on the first K' information bits."""
+        crc = (poly with its x^L term, L, K'): the CRC-aided stop (nrldpc_cfg.early_term = 2) on the first K' information bits.
+        algorithm: "min-sum" (default) or "sum-product" (flooding, the reference's comm.LDPCDecoder; alpha, beta and
+        llr_scale are not read; not with crc); set_algorithm() changes it between calls."""
+        alg = algorithm_code(algorithm)
         L = load()
         self._lib = L
         self._h = C.c_void_p()
@@ -216,6 +239,23 @@ class Codec:
         self.K, self.N_cw, self.kb, self.ncols, self.nrows = d.K, d.N_cw, d.kb, d.ncols, d.nrows
         self.i_ls, self.n_layers = d.i_ls, d.n_layers
         self.alpha, self.beta = float(d.alpha), float(d.beta)  # resolved check-node rule
+        if alg != ALG_MIN_SUM:
+            try:
+                self.set_algorithm(algorithm)
+            except Exception:
+                self.close()
+                raise
+
+    def set_algorithm(self, algorithm):
+        """nrldpc_set_algorithm: "min-sum" or "sum-product" for the calls that follow; no device work."""
+        check(self._lib.nrldpc_set_algorithm(self._h, algorithm_code(algorithm)))
+
+    @property
+    def algorithm(self):
+        """The handle's decoding algorithm ("min-sum" / "sum-product"), as the library reports it."""
+        a = C.c_int32()
+        check(self._lib.nrldpc_get_algorithm(self._h, C.byref(a)))
+        return algorithm_name(a.value)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -329,7 +369,8 @@ class CodecPool:
     Codec.decode call.  A device ordinal may repeat (several logical shards on one GPU)."""
 
     def __init__(self, bg, Z, device_ids, chunks_per_device=3, max_iter=50, n_layers=0, early_term=True, alpha=0.0,
-                 beta=0.0, llr_scale=0, llr_dtype=np.float32):
+                 beta=0.0, llr_scale=0, llr_dtype=np.float32, algorithm="min-sum"):
+        alg = algorithm_code(algorithm)
         L = load()
         self._lib = L
         self.llr_dtype = np.dtype(llr_dtype)
@@ -339,6 +380,12 @@ class CodecPool:
         ids = (C.c_int32 * len(self.device_ids))(*self.device_ids)
         self._p = C.c_void_p()
         check(L.nrldpc_pool_create(C.byref(cfg), ids, len(self.device_ids), int(chunks_per_device), C.byref(self._p)))
+        if alg != ALG_MIN_SUM:
+            try:
+                self.set_algorithm(algorithm)
+            except Exception:
+                self.close()
+                raise
         rows, cols, kb = {1: (46, 68, 22), 2: (42, 52, 10)}[int(bg)]
         self.K, self.N_cw = kb * int(Z), cols * int(Z)
 
@@ -362,6 +409,10 @@ class CodecPool:
         iters = np.empty(B, np.int32) if want_iters else None
         check(self._lib.nrldpc_pool_decode_packed(self._p, _ptr(llr), B, _ptr(packed), _ptr(iters)))
         return (packed, iters) if want_iters else packed
+
+    def set_algorithm(self, algorithm):
+        """nrldpc_pool_set_algorithm: "min-sum" or "sum-product" for every shard."""
+        check(self._lib.nrldpc_pool_set_algorithm(self._p, algorithm_code(algorithm)))
 
     def set_layers(self, n_layers):
         """nrldpc_pool_set_layers (LAYERS_AUTO: found once per call over the whole batch)."""

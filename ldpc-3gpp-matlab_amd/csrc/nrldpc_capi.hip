@@ -33,6 +33,7 @@
 #define NRLDPC_HOST_SPIN_US_DEFAULT 300 // see HostPool::spin_us
 #endif
 #include "nrldpc_sched.h"
+#include "nrldpc_bp.h"
 
 namespace {
 
@@ -417,6 +418,15 @@ struct nrldpc_codec {
     // timing
     bool timing = false, have_time = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // decoding algorithm of the calls that follow (nrldpc_set_algorithm); NRLDPC_ALG_SUM_PRODUCT: nrldpc_decode_bp.hip, whose
+    // column-ordered edge list (built at the first such launch) and message workspace belong to the handle.  bp_done is recorded
+    // behind every sum-product launch and the next one waits for it: a second call on another stream never reuses the workspace
+    // under the first
+    int32_t alg = NRLDPC_ALG_MIN_SUM;
+    DevBuf<uint16_t> d_bp_col; // col_ptr [ncols+1], then col_edge [nnz]
+    DevBuf<float> d_bp_ws;
+    hipEvent_t bp_done = nullptr;
+    bool bp_used = false;
 };
 
 namespace {
@@ -549,8 +559,58 @@ int32_t* next_work(nrldpc_codec* h, unsigned* slot) {
     return h->d_work.p + i;
 }
 
+// A sum-product launch (NRLDPC_ALG_SUM_PRODUCT) of `batch` codewords at d_llr, nl active rows: f32 or f16 LLRs as they are (no
+// int8 grid, no llr_scale; alpha and beta are not read).  Persistent workgroups, as many as the device holds at once, each with its
+// slice of the handle's workspace; ordered behind the handle's previous sum-product launch, whatever its stream.
+int bp_launch(nrldpc_codec* h, const void* d_llr, int batch, uint8_t* d_hard, int32_t* d_iters, float* d_app, hipStream_t stream,
+              int nl, int llr_kind) {
+    const nrldpc::Schedule& s = h->sched;
+    const nrldpc::BaseGraph& g = s.g;
+    if (!h->d_bp_col.p) { // column-ordered edge list, ascending edge (= row) order within a column
+        std::vector<uint16_t> tab((size_t)g.ncols + 1 + g.nnz, 0);
+        uint16_t* cp = tab.data();
+        uint16_t* ce = cp + g.ncols + 1;
+        for (int e = 0; e < g.nnz; ++e) ++cp[g.col[e] + 1];
+        for (int c = 0; c < g.ncols; ++c) cp[c + 1] += cp[c];
+        std::vector<uint16_t> fill(cp, cp + g.ncols);
+        for (int e = 0; e < g.nnz; ++e) ce[fill[g.col[e]]++] = (uint16_t)e;
+        HIP_TRY(h->d_bp_col.reserve(tab.size()));
+        HIP_TRY(hipMemcpy(h->d_bp_col.p, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
+    }
+    if (!h->bp_done) HIP_TRY(hipEventCreateWithFlags(&h->bp_done, hipEventDisableTiming));
+    const int threads = nrldpc::bp_threads(g.ncols, s.Z);
+    const size_t lds = nrldpc::bp_lds_bytes(g.ncols, s.Z);
+    int resident = 1;
+    const char* what = "";
+    if (hipError_t e = nrldpc::bp_resident(threads, lds, &resident, &what)) return hipfail(e, what);
+    const int grid = std::max(1, std::min(batch, resident));
+    const size_t stride = ((size_t)(g.nnz + g.ncols) * s.Z + 63) & ~(size_t)63;
+    if (h->d_bp_ws.n < stride * grid && h->bp_used) HIP_TRY(hipEventSynchronize(h->bp_done)); // the old workspace is freed below
+    HIP_TRY(h->d_bp_ws.reserve(stride * grid));
+    if (h->bp_used) HIP_TRY(hipStreamWaitEvent(stream, h->bp_done, 0));
+    nrldpc::BpArgs a;
+    memset(&a, 0, sizeof a);
+    a.llr = d_llr; a.hard = d_hard; a.iters = d_iters; a.app = d_app;
+    a.row_ptr = h->d_row_ptr.p; a.col = h->d_col.p; a.shift = h->d_shift.p;
+    a.col_ptr = h->d_bp_col.p; a.col_edge = h->d_bp_col.p + g.ncols + 1;
+    a.ws = h->d_bp_ws.p; a.ws_stride = stride;
+    a.batch = batch; a.Z = s.Z; a.nrows = g.nrows; a.ncols = g.ncols; a.kb = g.kb; a.nnz = g.nnz;
+    a.n_layers = nl; a.max_iter = h->cfg.max_iter; a.early_term = h->cfg.early_term ? 1 : 0;
+    a.llr_f16 = (llr_kind >= 0 ? llr_kind : (h->cfg.llr_dtype == NRLDPC_LLR_F16) ? NRLDPC_K_F16 : NRLDPC_K_F32) == NRLDPC_K_F16;
+    a.r_cap = (float)(2.0 * std::atanh(1.0 - 1e-15));
+    h->last_layers = nl;
+    begin_timing(h, stream);
+    hipError_t e = nrldpc::launch_bp_flood(a, grid, threads, lds, stream);
+    end_timing(h, stream);
+    if (e != hipSuccess) return hipfail(e, "sum-product decode kernel launch");
+    HIP_TRY(hipEventRecord(h->bp_done, stream));
+    h->bp_used = true;
+    return NRLDPC_OK;
+}
+
 int decode_launch(nrldpc_codec* h, const void* d_llr, int batch, uint8_t* d_hard, int32_t* d_iters, float* d_app,
                   hipStream_t stream, int nl, int llr_kind = -1) {
+    if (h->alg == NRLDPC_ALG_SUM_PRODUCT) return bp_launch(h, d_llr, batch, d_hard, d_iters, d_app, stream, nl, llr_kind);
     const nrldpc::Schedule& s = h->sched;
     nrldpc::DecArgs a = make_dec_args(h, d_llr, batch, d_hard, d_iters, d_app, nl, llr_kind);
     h->last_layers = nl;
@@ -733,6 +793,8 @@ void nrldpc_destroy(nrldpc_handle h) {
     DeviceScope scope(h->cfg.device_id);
     h->d_rot.release(); h->d_crc.release(); h->d_best.release(); h->pin_best.release(); h->d_work.release();
     h->d_row_ptr.release(); h->d_col.release(); h->d_shift.release();
+    h->d_bp_col.release(); h->d_bp_ws.release();
+    if (h->bp_done) (void)hipEventDestroy(h->bp_done);
     h->s_llr.release(); h->s_q.release(); h->s_hard.release(); h->s_bits.release(); h->s_pk.release(); h->s_iters.release(); h->s_app.release();
     for (auto& m : h->multi) { m.pin.release(); m.dev.release(); if (m.done) (void)hipEventDestroy(m.done); }
     for (int i = 0; i < nrldpc_codec::kSide; ++i) {
@@ -772,6 +834,21 @@ int nrldpc_set_layers(nrldpc_handle h, int32_t n_layers) {
     else if (n_layers == NRLDPC_LAYERS_ALL) h->layers = rows;
     else if (n_layers >= 4 && n_layers <= rows) h->layers = n_layers;
     else return fail(NRLDPC_ERR_UNSUPPORTED, "n_layers must be 0 (all), NRLDPC_LAYERS_AUTO or in 4..rows of the base graph");
+    return NRLDPC_OK;
+}
+
+int nrldpc_set_algorithm(nrldpc_handle h, int32_t algorithm) {
+    if (!h) return fail(NRLDPC_ERR_ARG, "null handle");
+    if (algorithm != NRLDPC_ALG_MIN_SUM && algorithm != NRLDPC_ALG_SUM_PRODUCT) return fail(NRLDPC_ERR_UNSUPPORTED, "unknown decoding algorithm");
+    if (algorithm == NRLDPC_ALG_SUM_PRODUCT && h->cfg.early_term == 2)
+        return fail(NRLDPC_ERR_UNSUPPORTED, "the CRC-aided stop (early_term = 2) is not available with sum-product decoding");
+    h->alg = algorithm;
+    return NRLDPC_OK;
+}
+
+int nrldpc_get_algorithm(nrldpc_handle h, int32_t* algorithm) {
+    if (!h || !algorithm) return fail(NRLDPC_ERR_ARG, "null handle/out");
+    *algorithm = h->alg;
     return NRLDPC_OK;
 }
 
@@ -881,7 +958,7 @@ int nrldpc_decode_multi_dev(int32_t n, const nrldpc_handle* hs, const void* cons
     (void)edges_read;
     struct Group { std::vector<nrldpc::DecArgs> args; std::vector<int32_t> start; size_t lds = 0; int grid = 0, threads = 0; };
     Group g[2][2][kClasses];
-    std::vector<int> routed;
+    std::vector<int> routed, bp;
     // layer count of every configuration: its handle's, or (NRLDPC_LAYERS_AUTO) read off its codewords -- all pre-pass kernels
     // are queued first and the stream is synchronised ONCE for the lot
     std::vector<int> nls((size_t)n, 0);
@@ -908,6 +985,7 @@ int nrldpc_decode_multi_dev(int32_t n, const nrldpc_handle* hs, const void* cons
         if (batch[i] == 0) continue;
         nrldpc_codec* h = hs[i];
         const nrldpc::Schedule& s = h->sched;
+        if (h->alg == NRLDPC_ALG_SUM_PRODUCT) { bp.push_back(i); continue; } // its own launch on the caller's stream, after the join
         // (a handle with the CRC-aided stop always gets a launch of its own: the shared kernel is built without it)
         if (h->cfg.early_term == 2 || ((long)batch[i] * s.Z >= env_rows && nrldpc::has_z64_kernel(s.g.bg, s.Z))) { routed.push_back(i); continue; }
         int cls = kClasses - 1;
@@ -939,7 +1017,14 @@ int nrldpc_decode_multi_dev(int32_t n, const nrldpc_handle* hs, const void* cons
                 host.insert(host.end(), reinterpret_cast<const char*>(q.start.data()),
                             reinterpret_cast<const char*>(q.start.data() + q.start.size()));
             }
-    if (nlaunch == 0) return NRLDPC_OK;
+    auto bp_launches = [&]() -> int { // the sum-product handles: nrldpc_decode_dev's launch, on the caller's stream
+        for (int i : bp) {
+            const int r = decode_launch(hs[i], d_llr[i], batch[i], d_hard[i], d_iters ? d_iters[i] : nullptr, nullptr, st, nls[i]);
+            if (r) return r;
+        }
+        return NRLDPC_OK;
+    };
+    if (nlaunch == 0) return bp_launches();
     // table slot: reused only after the launches that read it have completed (calls on different streams may overlap)
     nrldpc_codec::MultiSlot& m = own->multi[own->multi_next];
     own->multi_next = (own->multi_next + 1) % nrldpc_codec::kMultiSlots;
@@ -996,6 +1081,7 @@ int nrldpc_decode_multi_dev(int32_t n, const nrldpc_handle* hs, const void* cons
         }
     (void)hipEventRecord(m.done, st); // also on a failed launch: the copy above is in flight
     m.used = true;
+    if (rc == NRLDPC_OK) rc = bp_launches();
     return rc;
     NRLDPC_API_END
 }
@@ -1047,7 +1133,8 @@ int decode_host(nrldpc_handle h, const void* llr, int32_t batch, uint8_t* hard, 
     static const int env_threads = getenv("NRLDPC_HOST_THREADS") ? atoi(getenv("NRLDPC_HOST_THREADS")) : 16;
     // The copy threads quantise while they copy (1 byte per LLR on the wire instead of 2 / 4; nrldpc_host_quant.h) and a
     // small kernel expands each chunk to fp16 on the device (nrldpc_expand.hip).  NRLDPC_HOST_I8=0: A/B against the native format.
-    const bool i8 = !(getenv("NRLDPC_HOST_I8") && atoi(getenv("NRLDPC_HOST_I8")) == 0);
+    // Sum-product (NRLDPC_ALG_SUM_PRODUCT) ingests the caller's values unquantised: never this route.
+    const bool i8 = h->alg != NRLDPC_ALG_SUM_PRODUCT && !(getenv("NRLDPC_HOST_I8") && atoi(getenv("NRLDPC_HOST_I8")) == 0);
     const int hq_kind = f64 ? NRLDPC_HQ_F64 : h->cfg.llr_dtype == NRLDPC_LLR_F16 ? NRLDPC_HQ_F16 : NRLDPC_HQ_F32;
     const size_t host_eb = f64 ? 8 : eb; // element size of the caller's array
     static const int env_pipe = getenv("NRLDPC_HOST_PIPELINE") ? atoi(getenv("NRLDPC_HOST_PIPELINE")) : 1;
@@ -1539,6 +1626,16 @@ int nrldpc_pool_set_layers(nrldpc_pool_handle p, int32_t n_layers) {
         if (rc != NRLDPC_OK) return rc;
     }
     p->layers = p->hs[0]->layers;
+    return NRLDPC_OK;
+}
+
+int nrldpc_pool_set_algorithm(nrldpc_pool_handle p, int32_t algorithm) {
+    if (!p) return fail(NRLDPC_ERR_ARG, "null pool");
+    std::lock_guard<std::mutex> lk(p->m);
+    for (auto h : p->hs) { // the shards share one nrldpc_cfg: the first refusal comes before any shard changed
+        const int rc = nrldpc_set_algorithm(h, algorithm);
+        if (rc != NRLDPC_OK) return rc;
+    }
     return NRLDPC_OK;
 }
 

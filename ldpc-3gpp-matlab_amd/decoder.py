@@ -16,7 +16,7 @@ returns (a_hat[B][A], ok[B]) where ok[b] is False exactly when the reference wou
 import numpy as np
 
 from . import chain
-from ._capi import Codec, NRLDPCError
+from ._capi import Codec, NRLDPCError, algorithm_code
 from .nrldpc import NRLDPC
 
 
@@ -31,16 +31,20 @@ class NRLDPCDecoder(NRLDPC):
     _NONTUNABLE = NRLDPC._NONTUNABLE + ("I_HARQ",)
     _TUNABLE = NRLDPC._TUNABLE + ("iterations",)
 
-    def __init__(self, device_id=0, alpha=None, llr_scale=0, prune_layers=True, beta=0.0, crc_stop=False, **kw):
+    def __init__(self, device_id=0, alpha=None, llr_scale=0, prune_layers=True, beta=0.0, crc_stop=False, algorithm="min-sum", **kw):
         """prune_layers: True = the active rows from the object's parameters (active_layers(), kept at the maximum seen while
         HARQ state is pending); "auto" = NRLDPC_LAYERS_AUTO, read off every step's LLRs by the library (what the MEX gateway
-        does: it sees cw_tilde only, NRLDPCDecoder.m:265); False = every row, as the reference."""
+        does: it sees cw_tilde only, NRLDPCDecoder.m:265); False = every row, as the reference.
+        algorithm: "min-sum" (default: the layered min-sum kernels) or "sum-product" (flooding sum-product, the algorithm of the
+        reference's comm.LDPCDecoder, NRLDPCDecoder.m:120; alpha, beta and llr_scale are then not read, crc_stop is refused)."""
+        algorithm_code(algorithm)  # UnsupportedParameters for an unknown name, before any device work
         self._I_HARQ = 0        # NRLDPCDecoder.m:34
         self._iterations = 50   # NRLDPCDecoder.m:41
         super().__init__(**kw)
         self._device_id, self._alpha, self._llr_scale = device_id, alpha, llr_scale
         self._beta = beta  # read only with an explicit alpha (nrldpc_cfg.beta)
         self._prune = prune_layers
+        self._algorithm = algorithm
         self._crc_stop = bool(crc_stop)  # also stop a code block when its CRC holds (nrldpc_cfg.early_term = 2); the reference: False
         self._codec = None
         self._codec_layers = None
@@ -73,7 +77,7 @@ class NRLDPCDecoder(NRLDPC):
             self._codec = Codec(self.BG, self.Z_c, max_iter=self._setup_iterations, n_layers=n_layers,
                                 early_term=True, alpha=self._alpha or 0.0, beta=self._beta, llr_scale=self._llr_scale,
                                 llr_dtype=np.float32, device_id=self._device_id,
-                                crc=self.code_block_check() if self._crc_stop else None)
+                                crc=self.code_block_check() if self._crc_stop else None, algorithm=self._algorithm)
         else:
             self._codec.set_layers(n_layers)
         self._codec_layers = n_layers

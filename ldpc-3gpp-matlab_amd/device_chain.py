@@ -6,7 +6,7 @@ with no host loop and no PCIe traffic in between.  torch is used for device memo
 """
 import numpy as np
 
-from ._capi import LLR_F16, LLR_F32, Codec, NRLDPCError, crc_check_harq_dev, rate_recover_dev, tb_params
+from ._capi import LLR_F16, LLR_F32, Codec, NRLDPCError, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
 from .nrldpc import NRLDPC
 
 
@@ -38,7 +38,10 @@ class DeviceDecodeChain:
     code_block_CRC_passed flags (`cb_pass`); reset() clears them (:343-356).  CBGTI of `params` is honoured (:304)."""
 
     def __init__(self, params: NRLDPC, iterations=50, I_HARQ=0, alpha=None, llr_scale=0, prune_layers=True,
-                 llr_dtype=np.float16, device_id=0, beta=0.0, crc_stop=False):
+                 llr_dtype=None, device_id=0, beta=0.0, crc_stop=False, algorithm="min-sum"):
+        """llr_dtype: of the LLRs rate recovery hands the decoder; None = fp16 for "min-sum" (its kernels quantise to an int8 grid
+        anyway), f32 for "sum-product" (flooding sum-product, the reference's comm.LDPCDecoder: it ingests the values unquantised)."""
+        algorithm_code(algorithm)  # UnsupportedParameters for an unknown name, before any device work
         import torch
         self.torch = torch
         params.validate()
@@ -46,7 +49,8 @@ class DeviceDecodeChain:
         self.crc_stop = bool(crc_stop)  # nrldpc_cfg.early_term = 2: a code block also stops when its CRC holds
         self.iterations, self.I_HARQ = int(iterations), int(I_HARQ)
         self.alpha, self.beta, self.llr_scale, self.prune = alpha, beta, llr_scale, prune_layers
-        self.llr_dtype = np.dtype(llr_dtype)
+        self.algorithm = algorithm
+        self.llr_dtype = np.dtype(llr_dtype if llr_dtype is not None else np.float32 if algorithm == "sum-product" else np.float16)
         self.dev = torch.device("cuda", device_id)
         self.device_id = device_id
         self._codec, self._codec_layers, self._codec_code = None, None, None
@@ -75,7 +79,7 @@ class DeviceDecodeChain:
             self._codec_layers = None
             self._codec = Codec(self.p.BG, self.p.Z_c, max_iter=self.iterations, n_layers=n_layers, early_term=True,
                                 alpha=self.alpha or 0.0, beta=self.beta, llr_scale=self.llr_scale, llr_dtype=self.llr_dtype, device_id=self.device_id,
-                                crc=self.p.code_block_check() if self.crc_stop else None)
+                                crc=self.p.code_block_check() if self.crc_stop else None, algorithm=self.algorithm)
         elif self._codec_layers != n_layers:
             self._codec.set_layers(n_layers)
         self._codec_layers = n_layers

@@ -22,6 +22,9 @@
 //                                                       c_hat: K x C double in {0,1}; it: C x 1 int32 iterations run;
 //                                                       nl: the layer count the call ran with
 //   nrldpc_mex('set_layers', id, n_layers)              the count of the calls that follow (0 all, 4..rows, -1 auto)
+//   nrldpc_mex('set_algorithm', id, name)               'min-sum' (default) or 'sum-product': flooding sum-product, the algorithm
+//                                                       of comm.LDPCDecoder (NRLDPCDecoder.m:120), for the calls that follow
+//                                                       (nrldpc_set_algorithm; alpha and beta of 'create' are then not read)
 //   cw           = nrldpc_mex('encode', id, c)          c: K x C double in {0,1} (no NaN) -> (N+2*Z_c) x C double
 //   [a, b]       = nrldpc_mex('default_rule', BG, n_layers)
 //   nrldpc_mex('destroy', id)
@@ -29,6 +32,7 @@
 //   runs "parallel instances" by hand instead):
 //   pid          = nrldpc_mex('pool_create', BG, Z_c, iterations, device_ids [, chunks_per_device [, n_layers]])   (n_layers as above)
 //   [c_hat, it]  = nrldpc_mex('pool_decode', pid, cw_tilde)   any number of columns (double), dealt to the GPUs of the pool
+//   nrldpc_mex('pool_set_algorithm', pid, name)   as 'set_algorithm', for every GPU of the pool
 //   nrldpc_mex('pool_destroy', pid)
 // Errors carry the reference's two identifiers (NRLDPCDecoder.m:149, NRLDPC.m:240-294): callers that catch
 // 'ldpc_3gpp_matlab:UnsupportedParameters' and skip (plot_BLER_vs_SNR.m:173, testbench.m:51) keep working.
@@ -75,6 +79,17 @@ nrldpc_handle handle_of(const mxArray* a) {
 
 void need(bool ok, const char* msg) {
     if (!ok) mexErrMsgIdAndTxt("ldpc_3gpp_matlab:Error", "%s", msg);
+}
+
+// NRLDPC_ALG_* of an algorithm name; an unknown name is the reference's UnsupportedParameters
+int32_t algorithm_of(const mxArray* a) {
+    need(mxIsChar(a), "the algorithm should be 'min-sum' or 'sum-product'.");
+    char name[32];
+    mxGetString(a, name, sizeof name);
+    if (!strcmp(name, "min-sum")) return NRLDPC_ALG_MIN_SUM;
+    if (!strcmp(name, "sum-product")) return NRLDPC_ALG_SUM_PRODUCT;
+    mexErrMsgIdAndTxt("ldpc_3gpp_matlab:UnsupportedParameters", "unknown decoding algorithm '%s' ('min-sum' or 'sum-product').", name);
+    return -1;
 }
 
 } // namespace
@@ -134,6 +149,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(cmd, "set_layers")) {
         need(nrhs == 3, "set_layers needs a handle and a layer count.");
         check(nrldpc_set_layers(handle_of(prhs[1]), (int32_t)mxGetScalar(prhs[2])));
+    } else if (!strcmp(cmd, "set_algorithm")) {
+        need(nrhs == 3, "set_algorithm needs a handle and an algorithm name.");
+        check(nrldpc_set_algorithm(handle_of(prhs[1]), algorithm_of(prhs[2])));
     } else if (!strcmp(cmd, "encode")) {
         need(nrhs == 3 && mxIsDouble(prhs[2]) && !mxIsComplex(prhs[2]), "encode needs a handle and a real double matrix.");
         nrldpc_handle h = handle_of(prhs[1]);
@@ -211,6 +229,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (int c = 0; c < C; ++c)
             for (int k = 0; k < d.K; ++k) o[(size_t)c * d.K + k] = (double)((packed[(size_t)c * KB8 + (k >> 3)] >> (k & 7)) & 1);
         if (nlhs > 1) plhs[1] = it; else mxDestroyArray(it);
+    } else if (!strcmp(cmd, "pool_set_algorithm")) {
+        need(nrhs == 3, "pool_set_algorithm needs a pool id and an algorithm name.");
+        auto pit = g_pools.find((uint64_t)mxGetScalar(prhs[1]));
+        need(pit != g_pools.end(), "unknown or released pool.");
+        check(nrldpc_pool_set_algorithm(pit->second.p, algorithm_of(prhs[2])));
     } else if (!strcmp(cmd, "pool_destroy")) {
         need(nrhs == 2, "pool_destroy needs a pool id.");
         auto pit = g_pools.find((uint64_t)mxGetScalar(prhs[1]));
