@@ -386,7 +386,40 @@ template <int BG, int ZC, int L, bool FULL, int NL = BGT<BG>::ROWS, int H = -1> 
         return n;
     }
     float t[ncore];
-    float lam, m1, M1, M2;
+    // the row's two message magnitudes, each carrying the row's sign parity; MD is the magnitude of the edges that are not the
+    // minimum (M1, compare select) or what min_select() adds to M2 for them (D = M1 - M2, arithmetic select)
+    float lam, m1, MD, M2;
+
+    // Pass 2, the outgoing magnitude of an edge whose incoming value is x: M2 if |x| is the row's minimum m1, else M1.
+    // Arithmetic select: d = clamp01(|x| - m1) -- one v_sub_f32_e64 with the |x| and clamp modifiers -- and fma(d, D, M2), 2.4 + 3.0
+    // issue cycles against v_cmp_eq_f32_e64 + v_cndmask_b32 (4.2 + 2.1), no VCC, no SGPR pairs of masks, no hazard slots to fill.
+    // Exact, because every magnitude here is an integer-valued float below 2^21:
+    //   * m1 an integer: |x| - m1 is 0 for the edge(s) at the minimum and >= 1 for all others, so d is exactly 0 or 1 (ties at the
+    //     minimum all get M2, as with the compare), and (M1 - M2) + M2 is exact for integers up to 127;
+    //   * m1 not an integer: only the cap the pipelined search starts from (track3) is none, and m1 = cap means no edge was below
+    //     it, so m2 = cap too, M1 == M2, D == 0 and the fma returns M2 whatever fraction d is.
+    // Signed zeros.  With the row parity negative and M2 = 0 the compare form returns -0 where this one returns 0 * D + (-0) = +0
+    // (D = -M1 + M2 >= 0 there).  Nobody can tell: r = +-0 packs to the byte 0 either way; v = x + r is -0 only if x is -0; x = L -
+    // float(byte) is -0 only if L is -0; and no a-posteriori word L is ever -0 -- ingest() canonicalises -0, a sum of a non-zero x
+    // and a zero is x, and y + (-y) rounds to +0.  So the readers of sign bits (parity pass, esign, CRC fold, hard decision) and
+    // the soft output see what they saw.
+    __device__ __forceinline__ void set_mags(float mag1, float mag2, uint32_t S) {
+        // M | (S & signbit) in one v_bitop3_b32 (0xF8 = a | (b & c)); the signed M1 first, then D
+        const float M1 = __uint_as_float(__builtin_amdgcn_bitop3_b32(fbits(mag1), S, 0x80000000u, 0xF8));
+        M2 = __uint_as_float(__builtin_amdgcn_bitop3_b32(fbits(mag2), S, 0x80000000u, 0xF8));
+#if NRLDPC_Z64_ARITH_SELECT
+        MD = M1 - M2;
+#else
+        MD = M1;
+#endif
+    }
+    __device__ __forceinline__ float min_select(float x) const {
+#if NRLDPC_Z64_ARITH_SELECT
+        return __builtin_fmaf(clamp01(fabsf(x) - m1), MD, M2);
+#else
+        return (fabsf(x) == m1) ? M2 : MD;
+#endif
+    }
 
     __device__ __forceinline__ void load(const char* lds, const uint32_t (&R)[Z64<BG, ZC>::NBASE]) {
         static_for<ncore>([&](auto jc) {
@@ -493,22 +526,26 @@ template <int BG, int ZC, int L, bool FULL, int NL = BGT<BG>::ROWS, int H = -1> 
     // pass 2 for all (owned) edges after every part has been tracked
     template <class St> __device__ __forceinline__ void finish(St& st, char* lds, const uint32_t (&R)[Z64<BG, ZC>::NBASE], const DecArgs& a) {
         m1 = pm1;
-        // magnitudes carrying the row's sign parity: M | (S & signbit) in one v_bitop3_b32 (0xF8 = a | (b & c))
-        // a.beta holds 2^23 - beta here (set up by the pipelined kernels, see scale_mag_magic)
-        M1 = __uint_as_float(__builtin_amdgcn_bitop3_b32(fbits(scale_mag_magic(a.alpha, a.beta, pm1)), pS, 0x80000000u, 0xF8));
-        M2 = __uint_as_float(__builtin_amdgcn_bitop3_b32(fbits(scale_mag_magic(a.alpha, a.beta, pm2)), pS, 0x80000000u, 0xF8));
+        // a.alpha, a.beta hold the rule as magic_rule() prepared it (set up by the pipelined kernels)
+        set_mags(scale_mag_magic(a.alpha, a.beta, pm1), scale_mag_magic(a.alpha, a.beta, pm2), pS);
+#if !NRLDPC_Z64_ARITH_SELECT
         bool ismin[ncore]; // all compares first: keeps v_cmp -> v_cndmask hazard slots filled with useful work
         static_for<ncore>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             if constexpr (LayerZ64::owned(j)) ismin[j] = fabsf(t[j]) == m1;
         });
+#endif
         static_for<ncore>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             if constexpr (LayerZ64::owned(j)) {
                 constexpr int ce = LayerZ64::cidx(j);
                 constexpr int P = G::shift(e0 + j);
                 const float tj = t[j];
-                const float mag = ismin[j] ? M2 : M1;
+#if NRLDPC_Z64_ARITH_SELECT
+                const float mag = min_select(tj);
+#else
+                const float mag = ismin[j] ? M2 : MD;
+#endif
                 const float r = __uint_as_float(fbits(mag) ^ (fbits(tj) & 0x80000000u));
                 f32_to_byte<ce & 3>(st.rm[ce >> 2], r);
                 const float v = tj + r;
@@ -544,16 +581,15 @@ template <int BG, int ZC, int L, bool FULL, int NL = BGT<BG>::ROWS, int H = -1> 
             if constexpr (ncore % 2 == 1) S ^= pend;
         }
         m1 = mm1;
-        // magnitudes carrying the row's sign parity (M | (S & signbit), one v_bitop3_b32); the edge's own sign is
-        // xor-ed in per edge
-        M1 = __uint_as_float(__builtin_amdgcn_bitop3_b32(fbits(scale_mag(a, mm1)), S, 0x80000000u, 0xF8));
-        M2 = __uint_as_float(__builtin_amdgcn_bitop3_b32(fbits(scale_mag(a, mm2)), S, 0x80000000u, 0xF8));
+        // magnitudes carrying the row's sign parity; the edge's own sign is xor-ed in per edge
+        // (no cap here: the search starts from infinity, every |t| is finite, so m1 is always an integer)
+        set_mags(scale_mag(a, mm1), scale_mag(a, mm2), S);
         static_for<ncore>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int ce = ce0 + j;
             constexpr int P = G::shift(e0 + j);
             const float tj = t[j];
-            const float mag = (fabsf(tj) == m1) ? M2 : M1;
+            const float mag = min_select(tj);
             const float r = __uint_as_float(fbits(mag) ^ (fbits(tj) & 0x80000000u));
             f32_to_byte<ce & 3>(st.rm[ce >> 2], r);
             const float v = tj + r;
@@ -620,7 +656,7 @@ template <int BG, int ZC, int L, bool FULL, int NL = BGT<BG>::ROWS, int H = -1> 
     // early termination / soft output need the a-posteriori value of the row's extension-parity bit
     __device__ __forceinline__ void ext(const DecArgs& a, uint32_t& esign_lo, uint32_t& esign_hi, float* app_ext) const {
         if constexpr (HAS_EXT) {
-            const float mag = (fabsf(lam) == m1) ? M2 : M1;
+            const float mag = min_select(lam);
             const float r = __uint_as_float(fbits(mag) ^ (fbits(lam) & 0x80000000u));
             const float ae = lam + r;
             if constexpr (L - 4 < 32) esign_lo |= (fbits(ae) >> 31) << (L - 4);
@@ -1044,7 +1080,7 @@ __global__ __launch_bounds__(NCWG * z64_nwv(ZC) * 64, (z64_wpe<BG, ZC, NCWG, NL>
             // alpha and beta as VGPR values: the two fused multiply-adds per row then issue at the full rate (any VALU
             // op with an SGPR operand takes 4 cycles) and need no v_mov for their second scalar operand
             DecArgs av = a;
-            av.beta = 8388608.0f - a.beta; // see scale_mag_magic
+            magic_rule(av); // see scale_mag_magic
             asm volatile("" : "+v"(av.alpha), "+v"(av.beta));
             constexpr bool XF = z64_ext_float<BG, ZC, NCWG, NL>();
             if constexpr (XF) {
@@ -1163,7 +1199,7 @@ __global__ __launch_bounds__(NCWG * z64_nwv(ZC) * 64, (z64_wpe<BG, ZC, NCWG, NL>
         // barrier count of its workgroup until every codeword of it is done.
         const float cap = (127.49f + a.beta) / a.alpha;
         DecArgs av = a; // see the fixed-iteration path
-        av.beta = 8388608.0f - a.beta;
+        magic_rule(av); // see scale_mag_magic
         asm volatile("" : "+v"(av.alpha), "+v"(av.beta));
         int it = 1;
         bool all_done = false;

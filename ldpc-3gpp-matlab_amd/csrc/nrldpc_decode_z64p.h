@@ -234,7 +234,7 @@ __global__ __launch_bounds__(2 * z64p_rw(BG, ZC) * 64, (z64p_wpe<BG, ZC, NL>()))
         __syncthreads(); // the a-posteriori rings are complete
         const float cap = (127.49f + a.beta) / a.alpha; // see LayerZ64::track3
         DecArgs av = a;
-        av.beta = 8388608.0f - a.beta;
+        magic_rule(av); // see scale_mag_magic
 #if !NRLDPC_Z64S_RULE_SGPR
         asm volatile("" : "+v"(av.alpha), "+v"(av.beta));
 #endif
@@ -568,8 +568,8 @@ __global__ __launch_bounds__(z64p_rw(BG, ZC) * 64, (z64pg_wpe<BG, ZC>())) void n
     if constexpr (MODE != 0) {
         constexpr bool ETP = MODE == 2;
         const float cap = (127.49f + a.beta) / a.alpha; // see LayerZ64::track3
-        DecArgs av = a;                                  // alpha, 2^23 - beta as VGPR values (the one-thread-per-row kernel's choice)
-        av.beta = 8388608.0f - a.beta;
+        DecArgs av = a;                                  // the rule as VGPR values (the one-thread-per-row kernel's choice)
+        magic_rule(av); // see scale_mag_magic
         asm volatile("" : "+v"(av.alpha), "+v"(av.beta));
         GroupZ64<BG, ZC, 0, NL> g0;
         g0.template loads<false>(lds, R);

@@ -331,8 +331,8 @@ __global__ __launch_bounds__(2 * z64_nwv(ZC) * 64, (Z64S<BG, ZC, NL>::wpe())) vo
         else load_ext(std::integral_constant<int, NRLDPC_K_F32>{});
         __syncthreads(); // the a-posteriori rings are complete
         const float cap = (127.49f + a.beta) / a.alpha; // see LayerZ64::track3
-        DecArgs av = a;                                  // alpha, 2^23 - beta as VGPR values: see the one-thread-per-row kernel
-        av.beta = 8388608.0f - a.beta;
+        DecArgs av = a;                                  // the rule as scale_mag_magic wants it; VGPR values or not: NRLDPC_Z64S_RULE_SGPR
+        magic_rule(av); // see scale_mag_magic
 #if !NRLDPC_Z64S_RULE_SGPR
         asm volatile("" : "+v"(av.alpha), "+v"(av.beta));
 #endif

@@ -314,11 +314,43 @@ __device__ __forceinline__ bool crc_holds(const int* slots) {
     return r == 0 && slots[16] != 0;
 }
 
-// The same for the software-pipelined builds, with nbeta23 = 2^23 - beta held in a VGPR: v_fma + v_max + v_sub
-// (2.5 + 4 + 2.3 issue cycles; a separate v_rndne would cost 4 more).  The caller's search started from
-// (127.49 + beta)/alpha, so no upper clamp is needed.
+// Pass 2 of the compile-time-Z kernels without compares (LayerZ64::min_select, scale_mag_magic below): the min select and the lower
+// clamp of the row scaling as v_sub ... clamp, a 2-cycle instruction, in place of v_cmp + v_cndmask / v_max (4 cycles each on
+// gfx950, tools/ubench/valu_rate*.hip).  Same bits out.  -DNRLDPC_Z64_ARITH_SELECT=0 builds the compare forms (A/B).
+#ifndef NRLDPC_Z64_ARITH_SELECT
+#define NRLDPC_Z64_ARITH_SELECT 1
+#endif
+
+// clamp(x, 0, 1) folded into the instruction that produces x as its clamp modifier (v_sub_f32_e64 / v_add_f32_e64 ... clamp)
+__device__ __forceinline__ float clamp01(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
+
+// The same for the software-pipelined builds.  The caller's search started from (127.49 + beta)/alpha, so no upper clamp is
+// needed; the rule arrives prepared by magic_rule().
+#if NRLDPC_Z64_ARITH_SELECT
+// Everything scaled by 2^-23: a power of two commutes with round-to-nearest (nothing here is near the ends of the exponent
+// range), so y = fma(alpha 2^-23, m, (2^23 - beta) 2^-23) is 2^-23 times the fused multiply-add of scale_mag(), i.e. exactly
+// 1 + n 2^-23 with n = rint(alpha*m - beta) where n >= 0, and some value below 1 where n < 0.  y - 1 is then exact, the clamp
+// modifier of that subtraction is the lower clamp (n <= 127: the upper one never binds), and the product with 2^23 is n.
+// 2^-23 and not 2^-7, which would do as well, because it makes the subtrahend the inline constant 1.0: an e64 instruction takes
+// no literal, and a constant in an SGPR costs the 4-cycle issue the form is there to avoid.  v_fma + v_add clamp + v_mul
+// (2.5 + 2.4 + 2.3 issue cycles) against v_fma + v_max + v_sub (2.5 + 4.15 + 2.3).
+__device__ __forceinline__ float scale_mag_magic(float alpha_s, float nbeta_s, float m) {
+    return clamp01(__builtin_fmaf(alpha_s, m, nbeta_s) - 1.0f) * 8388608.0f;
+}
+#else
+// nbeta23 = 2^23 - beta: v_fma + v_max + v_sub (a separate v_rndne would cost 4 cycles more)
 __device__ __forceinline__ float scale_mag_magic(float alpha, float nbeta23, float m) {
     return fmaxf(__builtin_fmaf(alpha, m, nbeta23), 8388608.0f) - 8388608.0f;
+}
+#endif
+// the rule as scale_mag_magic() wants it, set up once per thread: alpha and beta of `av` are replaced
+__device__ __forceinline__ void magic_rule(DecArgs& av) {
+#if NRLDPC_Z64_ARITH_SELECT
+    av.alpha = av.alpha * 0x1p-23f;
+    av.beta = (8388608.0f - av.beta) * 0x1p-23f;
+#else
+    av.beta = 8388608.0f - av.beta;
+#endif
 }
 
 } // namespace nrldpc
