@@ -197,6 +197,45 @@ int nrldpc_decode_packed(nrldpc_handle h, const void* llr, int32_t batch, uint8_
 int nrldpc_decode_packed_layers(nrldpc_handle h, const void* llr, int32_t batch, uint8_t* hard_packed, int32_t* iters_out,
                                 int32_t n_layers);
 
+/* ---- whole-codeword hard decisions and final parity checks --------------------------------------------------------------
+ * comm.LDPCDecoder's OutputValue = 'Whole codeword' and FinalParityChecksOutputPort: nrldpc_decode[_dev] plus up to three more
+ * outputs per codeword, each left out by a null pointer (at least one must be given, else NRLDPC_ERR_ARG).  These entry points
+ * were added without a revision bump (NRLDPC_ABI_VERSION stays 6): a binding detects them by symbol, as nrldpc_set_algorithm.
+ *   - cw_packed: bit v is APP_v < 0 after the last iteration / sweep, for all N_cw = ncols*Z columns -- the rule the K
+ *     information bits follow (+inf and +-0 give 0, -inf gives 1), so the first K bits of cw_packed equal `hard`.  Columns above
+ *     the active rows carry the hard decision of what app_out reports for them.
+ *   - unsatisfied / checks_packed: the ACTIVE checks on those bits.  "Active" is the layer count the call ran with, which
+ *     nrldpc_last_layers reports: given (nrldpc_set_layers), taken from the handle, or found by NRLDPC_LAYERS_AUTO -- once per
+ *     call, over the whole batch.  unsatisfied == 0 says the codeword converged on the active rows, whatever the iteration count
+ *     (iters < max_iter under early_term = 1 implies it; iters == max_iter alone says nothing).
+ *   - hard, iters and every output are bit-identical to what nrldpc_decode_dev with app_out would give (the outputs derived from
+ *     app_out by the rule above); they do not depend on the batch or on how it is split.
+ *   - early_term == 2 (the CRC-aided stop) is refused with NRLDPC_ERR_UNSUPPORTED, as app_out is.
+ *   - NRLDPC_ALG_SUM_PRODUCT: the sum-product kernel writes the outputs itself (no scratch, no second kernel).
+ *     NRLDPC_ALG_MIN_SUM: the call runs the soft-output route of the decoder (app_out) into a scratch owned by the handle, then a
+ *     finish kernel on the same stream; the scratch holds at most NRLDPC_CW_SCRATCH_BYTES, so the call walks the batch in chunks
+ *     of floor(NRLDPC_CW_SCRATCH_BYTES / (4 * N_cw)) codewords (the NRLDPC_LAYERS_AUTO count and the check-node rule are resolved
+ *     once, before the first chunk).  This is slower than a plain decode: DESIGN.md section 4.11.  A second call on the same handle
+ *     is ordered behind the previous one, whatever its stream.
+ * Pool (nrldpc_pool_*) and nrldpc_decode_multi_dev variants do not exist: out of scope.
+ * sizeof(nrldpc_cw_out) == 32 on LP64 (the library static_asserts it; a binding can compare its own structure's size). */
+#define NRLDPC_CW_SCRATCH_BYTES (64u << 20) /* 64 MiB: bound of the handle-owned scratch of nrldpc_decode_cw[_dev] (min-sum) */
+typedef struct nrldpc_cw_out {
+    uint32_t struct_size;    /* = sizeof(nrldpc_cw_out); any other value: NRLDPC_ERR_ARG */
+    uint8_t* cw_packed;      /* [batch][ceil(N_cw/8)]: bit v of a codeword in byte v/8 at bit v%8 (LSB first); N_cw = ncols*Z is a multiple of
+                                4, not of 8, when Z is odd: the unused bits of a codeword's last byte are 0; nullable */
+    int32_t* unsatisfied;    /* [batch]: number of ACTIVE checks that fail on the final hard decisions; 0 = converged; nullable */
+    uint8_t* checks_packed;  /* [batch][ceil(nrows*Z/8)]: check (l*Z+z) as one bit, same packing; rows >= the active count are 0; nullable */
+} nrldpc_cw_out;
+/* d_out is a HOST structure whose three pointers are device memory; asynchronous on `stream` (under NRLDPC_LAYERS_AUTO the stream is
+ * synchronised once, as by nrldpc_decode_dev).  d_llr: F32 / F16. */
+int nrldpc_decode_cw_dev(nrldpc_handle h, const void* d_llr, int32_t batch, uint8_t* d_hard, int32_t* d_iters_out,
+                         const nrldpc_cw_out* d_out, void* stream);
+/* Host memory throughout; llr in cfg.llr_dtype (F32 / F16 / F64, F64 narrowed to F32 on the host).  The caller's array is staged in
+ * its own format: never the int8 wire route of large nrldpc_decode batches.  Synchronous. */
+int nrldpc_decode_cw(nrldpc_handle h, const void* llr, int32_t batch, uint8_t* hard, int32_t* iters_out,
+                     const nrldpc_cw_out* out);
+
 /* The quantisation nrldpc_decode applies to large host batches while it copies them into its pinned staging
  * buffers (so that 1 byte per LLR crosses PCIe instead of 4): dst[i] = NaN ? 0 : rint(clamp(float(src[i]) * llr_scale,
  * +-127)) as int8 -- the kernels' own ingest arithmetic, operation for operation -- with +inf (filler bits,

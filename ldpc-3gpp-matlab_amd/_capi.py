@@ -65,6 +65,18 @@ class Dims(C.Structure):
                 ("K", C.c_int32), ("N_cw", C.c_int32), ("n_layers", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float)]
 
 
+class CwOut(C.Structure):
+    """nrldpc_cw_out: the extra outputs of nrldpc_decode_cw[_dev], each left out by a null pointer; struct_size is filled in by the
+    constructor (positional arguments start at cw_packed)."""
+    _fields_ = [("struct_size", C.c_uint32), ("cw_packed", C.c_void_p), ("unsatisfied", C.c_void_p), ("checks_packed", C.c_void_p)]
+
+
+def _cw_out_init(self, *args, **kw):
+    C.Structure.__init__(self, C.sizeof(CwOut), *args, **kw)
+
+
+CwOut.__init__ = _cw_out_init
+
 MAX_C = 160
 
 
@@ -93,7 +105,7 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_pool_destroy", "nrldpc_pool_decode_dev", "nrldpc_pool_size", "nrldpc_abi_version", "nrldpc_decode_packed",
            "nrldpc_set_layers", "nrldpc_set_llr_dtype", "nrldpc_last_layers", "nrldpc_count_layers", "nrldpc_pool_set_layers", "nrldpc_pool_decode_packed",
            "nrldpc_decode_packed_layers", "nrldpc_pool_set_timing", "nrldpc_pool_last_kernel_ms", "nrldpc_last_host_phases", "nrldpc_payload_bits_dev",
-           "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm"]
+           "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm", "nrldpc_decode_cw", "nrldpc_decode_cw_dev"]
 
 _lib = None
 
@@ -153,6 +165,8 @@ def load():
     L.nrldpc_payload_bits_dev.argtypes = [C.c_uint64, C.c_uint64, i32, i32, vp, vp]
     L.nrldpc_pool_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.nrldpc_decode_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.nrldpc_decode_cw.argtypes = [vp, vp, i32, vp, vp, C.POINTER(CwOut)]
+    L.nrldpc_decode_cw_dev.argtypes = [vp, vp, i32, vp, vp, C.POINTER(CwOut), vp]
     L.nrldpc_quantise_llr.argtypes = [vp, vp, C.c_int64, i32, i32]
     L.nrldpc_decode_multi_dev.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), vp]
     L.nrldpc_encode.argtypes = [vp, vp, i32, vp]
@@ -309,6 +323,27 @@ class Codec:
             out += (app,)
         return out[0] if len(out) == 1 else out
 
+    def decode_cw(self, llr, want_checks=False):
+        """nrldpc_decode_cw: (hard, iters, cw, unsatisfied[, checks]) -- decode()'s hard decisions and iteration counts, the whole
+        codeword's hard decisions cw [B][N_cw] (uint8; cw[:, :K] == hard), the number of active parity checks that fail on them
+        (0 = converged) and, with want_checks, every check as a uint8 [B][nrows*Z] (row l, shift z at l*Z + z; inactive rows 0)."""
+        llr = np.ascontiguousarray(llr, self.llr_dtype)
+        if llr.size % self.N_cw:
+            raise NRLDPCError("llr should hold a whole number of codewords of length %d" % self.N_cw)
+        B = llr.size // self.N_cw
+        nchk = self.nrows * self.Z
+        hard = np.empty((B, self.K), np.uint8)
+        iters = np.empty(B, np.int32)
+        cw = np.empty((B, (self.N_cw + 7) // 8), np.uint8)
+        unsat = np.empty(B, np.int32)
+        chk = np.empty((B, (nchk + 7) // 8), np.uint8) if want_checks else None
+        o = CwOut(cw.ctypes.data, unsat.ctypes.data, chk.ctypes.data if want_checks else None)
+        check(self._lib.nrldpc_decode_cw(self._h, _ptr(llr), B, _ptr(hard), _ptr(iters), C.byref(o)))
+        out = (hard, iters, np.unpackbits(cw, axis=1, bitorder="little")[:, :self.N_cw], unsat)
+        if want_checks:
+            out += (np.unpackbits(chk, axis=1, bitorder="little")[:, :nchk],)
+        return out
+
     def decode_packed(self, llr, want_iters=False, out=None, n_layers=None):
         """nrldpc_decode_packed: hard decisions as [B][ceil(K/8)] bytes, bit k of a codeword in byte k // 8 at bit k % 8
         (np.unpackbits(out, axis=1, bitorder="little")[:, :K] gives decode()'s array).  out: see decode().
@@ -341,6 +376,12 @@ class Codec:
     def decode_dev(self, d_llr, batch, d_hard, d_iters=None, d_app=None, stream=0):
         check(self._lib.nrldpc_decode_dev(self._h, _ptr(d_llr), int(batch), _ptr(d_hard), _ptr(d_iters),
                                           _ptr(d_app), C.c_void_p(stream)))
+
+    def decode_cw_dev(self, d_llr, batch, d_hard, d_iters=None, d_cw_packed=None, d_unsatisfied=None, d_checks_packed=None, stream=0):
+        """nrldpc_decode_cw_dev on raw device addresses: d_cw_packed [batch][ceil(N_cw/8)], d_unsatisfied [batch] int32, d_checks_packed
+        [batch][ceil(nrows*Z/8)], each optional (at least one); bit i of a row in byte i // 8 at bit i % 8."""
+        o = CwOut(*[int(x) if x else None for x in (d_cw_packed, d_unsatisfied, d_checks_packed)])
+        check(self._lib.nrldpc_decode_cw_dev(self._h, _ptr(d_llr), int(batch), _ptr(d_hard), _ptr(d_iters), C.byref(o), C.c_void_p(stream)))
 
     def encode_dev(self, d_info, batch, d_cw, stream=0):
         check(self._lib.nrldpc_encode_dev(self._h, _ptr(d_info), int(batch), _ptr(d_cw), C.c_void_p(stream)))

@@ -19,6 +19,10 @@ struct BpArgs {
     uint8_t* hard;      // [batch][kb*Z]
     int32_t* iters;     // [batch], nullable
     float* app;         // [batch][ncols*Z], nullable
+    // nrldpc_cw_out (include/nrldpc.h), each nullable; with any of them the launch carries CW_LDS_BYTES (nrldpc_cwout.h) more LDS
+    uint8_t* cw_packed;     // [batch][ceil(ncols*Z/8)]
+    int32_t* unsatisfied;   // [batch]
+    uint8_t* checks_packed; // [batch][ceil(nrows*Z/8)]
     const uint16_t* row_ptr; // base graph, row-ordered edges (the handle's d_row_ptr / d_col / d_shift: shifts mod Z)
     const uint8_t* col;
     const uint16_t* shift;

@@ -34,6 +34,9 @@
 #endif
 #include "nrldpc_sched.h"
 #include "nrldpc_bp.h"
+#include "nrldpc_cwout.h"
+
+static_assert(sizeof(nrldpc_cw_out) == 32, "nrldpc_cw_out: the size include/nrldpc.h states");
 
 namespace {
 
@@ -427,6 +430,13 @@ struct nrldpc_codec {
     DevBuf<float> d_bp_ws;
     hipEvent_t bp_done = nullptr;
     bool bp_used = false;
+    // nrldpc_decode_cw[_dev] on a min-sum handle: the soft output of one chunk (at most NRLDPC_CW_SCRATCH_BYTES), which the finish
+    // kernel (nrldpc_cwout.hip) reads.  cw_done is recorded behind every such call and the next one waits for it, as bp_done
+    DevBuf<float> d_cw_app;
+    hipEvent_t cw_done = nullptr;
+    bool cw_used = false;
+    DevBuf<uint8_t> s_cw, s_chk; // host-entry staging of nrldpc_decode_cw
+    DevBuf<int32_t> s_unsat;
 };
 
 namespace {
@@ -562,8 +572,9 @@ int32_t* next_work(nrldpc_codec* h, unsigned* slot) {
 // A sum-product launch (NRLDPC_ALG_SUM_PRODUCT) of `batch` codewords at d_llr, nl active rows: f32 or f16 LLRs as they are (no
 // int8 grid, no llr_scale; alpha and beta are not read).  Persistent workgroups, as many as the device holds at once, each with its
 // slice of the handle's workspace; ordered behind the handle's previous sum-product launch, whatever its stream.
+// cw (nullable): nrldpc_cw_out of the call, device pointers -- written by the kernel's output stage
 int bp_launch(nrldpc_codec* h, const void* d_llr, int batch, uint8_t* d_hard, int32_t* d_iters, float* d_app, hipStream_t stream,
-              int nl, int llr_kind) {
+              int nl, int llr_kind, const nrldpc_cw_out* cw = nullptr) {
     const nrldpc::Schedule& s = h->sched;
     const nrldpc::BaseGraph& g = s.g;
     if (!h->d_bp_col.p) { // column-ordered edge list, ascending edge (= row) order within a column
@@ -579,7 +590,7 @@ int bp_launch(nrldpc_codec* h, const void* d_llr, int batch, uint8_t* d_hard, in
     }
     if (!h->bp_done) HIP_TRY(hipEventCreateWithFlags(&h->bp_done, hipEventDisableTiming));
     const int threads = nrldpc::bp_threads(g.ncols, s.Z);
-    const size_t lds = nrldpc::bp_lds_bytes(g.ncols, s.Z);
+    const size_t lds = nrldpc::bp_lds_bytes(g.ncols, s.Z) + (cw ? nrldpc::CW_LDS_BYTES : 0);
     int resident = 1;
     const char* what = "";
     if (hipError_t e = nrldpc::bp_resident(threads, lds, &resident, &what)) return hipfail(e, what);
@@ -591,6 +602,7 @@ int bp_launch(nrldpc_codec* h, const void* d_llr, int batch, uint8_t* d_hard, in
     nrldpc::BpArgs a;
     memset(&a, 0, sizeof a);
     a.llr = d_llr; a.hard = d_hard; a.iters = d_iters; a.app = d_app;
+    if (cw) { a.cw_packed = cw->cw_packed; a.unsatisfied = cw->unsatisfied; a.checks_packed = cw->checks_packed; }
     a.row_ptr = h->d_row_ptr.p; a.col = h->d_col.p; a.shift = h->d_shift.p;
     a.col_ptr = h->d_bp_col.p; a.col_edge = h->d_bp_col.p + g.ncols + 1;
     a.ws = h->d_bp_ws.p; a.ws_stride = stride;
@@ -621,6 +633,59 @@ int decode_launch(nrldpc_codec* h, const void* d_llr, int batch, uint8_t* d_hard
     end_timing(h, stream);
     if (a.work) (void)hipEventRecord(h->work_done[wslot], stream);
     if (e != hipSuccess) return hipfail(e, "decode kernel launch");
+    return NRLDPC_OK;
+}
+
+// nrldpc_decode_cw_dev behind its argument checks: `batch` codewords at d_llr (device; llr_kind as decode_launch) with the outputs
+// of *out (device pointers).  Sum-product: one launch, the kernel writes them.  Min-sum: chunks of the soft-output route into the
+// handle's scratch, each followed by the finish kernel on the same stream.
+int decode_cw_launch(nrldpc_codec* h, const void* d_llr, int batch, uint8_t* d_hard, int32_t* d_iters, const nrldpc_cw_out* out,
+                     hipStream_t stream) {
+    const nrldpc::Schedule& s = h->sched;
+    const nrldpc::BaseGraph& g = s.g;
+    int nl = 0;
+    int rc = resolve_layers_dev(h, d_llr, batch, stream, &nl); // NRLDPC_LAYERS_AUTO: once, over the whole batch
+    if (rc) return rc;
+    if (h->alg == NRLDPC_ALG_SUM_PRODUCT) return bp_launch(h, d_llr, batch, d_hard, d_iters, nullptr, stream, nl, -1, out);
+    const size_t N = (size_t)g.ncols * s.Z, K = (size_t)g.kb * s.Z, eb = llr_elem_bytes(h->cfg.llr_dtype);
+    const size_t cbytes = ((size_t)g.nrows * s.Z + 7) / 8;
+    const int chunk = (int)std::min<size_t>((size_t)batch, (size_t)NRLDPC_CW_SCRATCH_BYTES / (4 * N));
+    if (!h->cw_done) HIP_TRY(hipEventCreateWithFlags(&h->cw_done, hipEventDisableTiming));
+    if (h->d_cw_app.n < (size_t)chunk * N && h->cw_used) HIP_TRY(hipEventSynchronize(h->cw_done)); // the old scratch is freed below
+    HIP_TRY(h->d_cw_app.reserve((size_t)chunk * N));
+    if (h->cw_used) HIP_TRY(hipStreamWaitEvent(stream, h->cw_done, 0));
+    for (int c0 = 0; c0 < batch; c0 += chunk) {
+        const int n = std::min(chunk, batch - c0);
+        rc = decode_launch(h, static_cast<const char*>(d_llr) + (size_t)c0 * N * eb, n, d_hard + (size_t)c0 * K, d_iters ? d_iters + c0 : nullptr,
+                           h->d_cw_app.p, stream, nl);
+        if (rc) break;
+        nrldpc::CwFinishArgs a;
+        memset(&a, 0, sizeof a);
+        a.app = h->d_cw_app.p;
+        a.cw_packed = out->cw_packed ? out->cw_packed + (size_t)c0 * ((N + 7) / 8) : nullptr;
+        a.unsatisfied = out->unsatisfied ? out->unsatisfied + c0 : nullptr;
+        a.checks_packed = out->checks_packed ? out->checks_packed + (size_t)c0 * cbytes : nullptr;
+        a.row_ptr = h->d_row_ptr.p; a.col = h->d_col.p; a.shift = h->d_shift.p;
+        a.batch = n; a.Z = s.Z; a.nrows = g.nrows; a.ncols = g.ncols; a.nnz = g.nnz; a.n_layers = nl;
+        if (hipError_t e = nrldpc::launch_cw_finish(a, stream)) { rc = hipfail(e, "codeword finish kernel launch"); break; }
+    }
+    // recorded on failure too: whatever was queued still owns the scratch
+    if (hipEventRecord(h->cw_done, stream) == hipSuccess) h->cw_used = true;
+    return rc;
+}
+
+// the argument checks nrldpc_decode_cw and nrldpc_decode_cw_dev share
+int check_cw_args(nrldpc_codec* h, const void* llr, int batch, const uint8_t* hard, const nrldpc_cw_out* out) {
+    if (!h) return fail(NRLDPC_ERR_ARG, "null handle");
+    if (batch < 0) return fail(NRLDPC_ERR_ARG, "negative batch");
+    if (!out) return fail(NRLDPC_ERR_ARG, "null nrldpc_cw_out");
+    if (out->struct_size != (uint32_t)sizeof(nrldpc_cw_out))
+        return fail(NRLDPC_ERR_ARG, "nrldpc_cw_out.struct_size does not match this library (set it to sizeof(nrldpc_cw_out))");
+    if (!out->cw_packed && !out->unsatisfied && !out->checks_packed)
+        return fail(NRLDPC_ERR_ARG, "nrldpc_cw_out: at least one of cw_packed, unsatisfied, checks_packed must be given");
+    if (h->cfg.early_term == 2)
+        return fail(NRLDPC_ERR_UNSUPPORTED, "whole-codeword outputs are not available with the CRC-aided stop (early_term = 2)");
+    if (batch > 0 && (!llr || !hard)) return fail(NRLDPC_ERR_ARG, "null llr/hard pointer");
     return NRLDPC_OK;
 }
 
@@ -795,6 +860,8 @@ void nrldpc_destroy(nrldpc_handle h) {
     h->d_row_ptr.release(); h->d_col.release(); h->d_shift.release();
     h->d_bp_col.release(); h->d_bp_ws.release();
     if (h->bp_done) (void)hipEventDestroy(h->bp_done);
+    h->d_cw_app.release(); h->s_cw.release(); h->s_chk.release(); h->s_unsat.release();
+    if (h->cw_done) (void)hipEventDestroy(h->cw_done);
     h->s_llr.release(); h->s_q.release(); h->s_hard.release(); h->s_bits.release(); h->s_pk.release(); h->s_iters.release(); h->s_app.release();
     for (auto& m : h->multi) { m.pin.release(); m.dev.release(); if (m.done) (void)hipEventDestroy(m.done); }
     for (int i = 0; i < nrldpc_codec::kSide; ++i) {
@@ -910,6 +977,18 @@ int nrldpc_decode_dev(nrldpc_handle h, const void* d_llr, int32_t batch, uint8_t
     const int rc = resolve_layers_dev(h, d_llr, batch, static_cast<hipStream_t>(stream), &nl);
     if (rc) return rc;
     return decode_launch(h, d_llr, batch, d_hard, d_iters_out, d_app_out, static_cast<hipStream_t>(stream), nl);
+}
+
+int nrldpc_decode_cw_dev(nrldpc_handle h, const void* d_llr, int32_t batch, uint8_t* d_hard, int32_t* d_iters_out,
+                         const nrldpc_cw_out* d_out, void* stream) {
+    NRLDPC_API_BEGIN
+    const int rc = check_cw_args(h, d_llr, batch, d_hard, d_out);
+    if (rc) return rc;
+    if (batch == 0) return NRLDPC_OK;
+    if (h->cfg.llr_dtype == NRLDPC_LLR_F64) return fail(NRLDPC_ERR_ARG, "f64 LLRs are accepted by the host entry point only");
+    DEVICE_SCOPE(h);
+    return decode_cw_launch(h, d_llr, batch, d_hard, d_iters_out, d_out, static_cast<hipStream_t>(stream));
+    NRLDPC_API_END
 }
 
 int nrldpc_decode_multi_dev(int32_t n, const nrldpc_handle* hs, const void* const* d_llr, const int32_t* batch,
@@ -1403,6 +1482,42 @@ extern "C" {
 
 int nrldpc_decode(nrldpc_handle h, const void* llr, int32_t batch, uint8_t* hard, int32_t* iters_out, float* app_out) {
     return decode_host(h, llr, batch, hard, iters_out, app_out, false);
+}
+
+int nrldpc_decode_cw(nrldpc_handle h, const void* llr, int32_t batch, uint8_t* hard, int32_t* iters_out, const nrldpc_cw_out* out) {
+    NRLDPC_API_BEGIN
+    int rc = check_cw_args(h, llr, batch, hard, out);
+    if (rc) return rc;
+    if (batch == 0) return NRLDPC_OK;
+    DEVICE_SCOPE(h);
+    const nrldpc::Schedule& s = h->sched;
+    const size_t B = (size_t)batch, N = (size_t)s.g.ncols * s.Z, K = (size_t)s.g.kb * s.Z, cbytes = ((size_t)s.g.nrows * s.Z + 7) / 8;
+    const size_t eb = llr_elem_bytes(h->cfg.llr_dtype); // on the device: the caller's format, MATLAB doubles narrowed to f32 here
+    HIP_TRY(h->s_llr.reserve(B * N * eb));
+    HIP_TRY(h->s_hard.reserve(B * K));
+    if (iters_out) HIP_TRY(h->s_iters.reserve(B));
+    nrldpc_cw_out d = *out;
+    if (out->cw_packed) { HIP_TRY(h->s_cw.reserve(B * ((N + 7) / 8))); d.cw_packed = h->s_cw.p; }
+    if (out->unsatisfied) { HIP_TRY(h->s_unsat.reserve(B)); d.unsatisfied = h->s_unsat.p; }
+    if (out->checks_packed) { HIP_TRY(h->s_chk.reserve(B * cbytes)); d.checks_packed = h->s_chk.p; }
+    const void* src = llr;
+    if (h->cfg.llr_dtype == NRLDPC_LLR_F64) {
+        h->h_narrow.resize(B * N);
+        const double* x = static_cast<const double*>(llr);
+        for (size_t i = 0; i < B * N; ++i) h->h_narrow[i] = (float)x[i];
+        src = h->h_narrow.data();
+    }
+    HIP_TRY(hipMemcpyAsync(h->s_llr.p, src, B * N * eb, hipMemcpyHostToDevice, nullptr));
+    rc = decode_cw_launch(h, h->s_llr.p, batch, h->s_hard.p, iters_out ? h->s_iters.p : nullptr, &d, nullptr);
+    if (rc) { (void)hipStreamSynchronize(nullptr); return rc; }
+    HIP_TRY(hipMemcpyAsync(hard, h->s_hard.p, B * K, hipMemcpyDeviceToHost, nullptr));
+    if (iters_out) HIP_TRY(hipMemcpyAsync(iters_out, h->s_iters.p, B * 4, hipMemcpyDeviceToHost, nullptr));
+    if (out->cw_packed) HIP_TRY(hipMemcpyAsync(out->cw_packed, d.cw_packed, B * ((N + 7) / 8), hipMemcpyDeviceToHost, nullptr));
+    if (out->unsatisfied) HIP_TRY(hipMemcpyAsync(out->unsatisfied, d.unsatisfied, B * 4, hipMemcpyDeviceToHost, nullptr));
+    if (out->checks_packed) HIP_TRY(hipMemcpyAsync(out->checks_packed, d.checks_packed, B * cbytes, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return NRLDPC_OK;
+    NRLDPC_API_END
 }
 
 int nrldpc_decode_packed(nrldpc_handle h, const void* llr, int32_t batch, uint8_t* hard_packed, int32_t* iters_out) {

@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "nrldpc_bp.h"
+#include "nrldpc_cwout.h"
 
 namespace nrldpc {
 
@@ -40,6 +41,11 @@ __global__ __launch_bounds__(BP_MAX_THREADS) void nrldpc_bp_flood_kernel(const B
     uint16_t* cp = ce + T_E;
     float* app = reinterpret_cast<float*>(lds + BP_TAB_BYTES);
     const int Z = a.Z, N = a.ncols * Z, K = a.kb * Z, nl = a.n_layers;
+    // whole-codeword bits and final parity checks (nrldpc_cw_out): the bit image and the wave counts sit behind APP (N is a
+    // multiple of 4, so the offset is a multiple of 16 bytes); the launch carries those bytes only when an output is wanted
+    const bool cw_out = a.cw_packed || a.unsatisfied || a.checks_packed;
+    unsigned long long* cw_bits = reinterpret_cast<unsigned long long*>(lds + BP_TAB_BYTES + (size_t)N * 4);
+    int* cw_red = reinterpret_cast<int*>(cw_bits + CW_BIT_WORDS);
     const int tid = threadIdx.x, nt = blockDim.x;
     for (int i = tid; i <= a.nrows; i += nt) rp[i] = a.row_ptr[i];
     for (int i = tid; i < a.nnz; i += nt) { ecol[i] = a.col[i]; esh[i] = a.shift[i]; ce[i] = a.col_edge[i]; }
@@ -132,6 +138,8 @@ __global__ __launch_bounds__(BP_MAX_THREADS) void nrldpc_bp_flood_kernel(const B
         if (a.app)
             for (int v = tid; v < N; v += nt) a.app[(size_t)b * N + v] = app[v];
         if (a.iters && tid == 0) a.iters[b] = it;
+        if (cw_out) // from the APP in LDS: the routine the finish kernel runs on app_out, so the bits are the same
+            cw_finish_codeword(app, b, N, Z, a.nrows, nl, rp, ecol, esh, cw_bits, cw_red, a.cw_packed, a.unsatisfied, a.checks_packed);
         __syncthreads(); // APP, r and lambda belong to the next codeword from here on
     }
 }

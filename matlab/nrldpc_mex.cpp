@@ -21,6 +21,10 @@
 //                                                       makes: with MATLAB doubles the host side is bound by reading the array)
 //                                                       c_hat: K x C double in {0,1}; it: C x 1 int32 iterations run;
 //                                                       nl: the layer count the call ran with
+//   [cw_hat, unsat, it] = nrldpc_mex('decode_cw', id, cw_tilde)      comm.LDPCDecoder's OutputValue = 'Whole codeword' with
+//                                                       FinalParityChecksOutputPort (nrldpc_decode_cw): cw_hat (N+2*Z_c) x C logical,
+//                                                       the hard decision of every column; unsat: 1 x C int32, the active parity
+//                                                       checks that fail on cw_hat (0 = converged); it: C x 1 int32
 //   nrldpc_mex('set_layers', id, n_layers)              the count of the calls that follow (0 all, 4..rows, -1 auto)
 //   nrldpc_mex('set_algorithm', id, name)               'min-sum' (default) or 'sum-product': flooding sum-product, the algorithm
 //                                                       of comm.LDPCDecoder (NRLDPCDecoder.m:120), for the calls that follow
@@ -47,6 +51,10 @@
 
 #include "mex.h"
 #include "nrldpc.h"
+
+// MathWorks' C Matrix API (matrix.h); restated because the stub header the CPU suite compile-checks this file against
+// (tests/mex_stub/mex.h) declares only what the gateway used before 'decode_cw'
+extern "C" mxArray* mxCreateLogicalMatrix(mwSize m, mwSize n);
 
 namespace {
 
@@ -146,6 +154,32 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             check(nrldpc_last_layers(h, &nl));
             plhs[2] = mxCreateDoubleScalar((double)nl);
         }
+    } else if (!strcmp(cmd, "decode_cw")) {
+        need(nrhs == 3 && (mxIsDouble(prhs[2]) || mxIsSingle(prhs[2])) && !mxIsComplex(prhs[2]),
+             "decode_cw needs a handle and a real double or single matrix.");
+        nrldpc_handle h = handle_of(prhs[1]);
+        nrldpc_dims d;
+        d.struct_size = sizeof d;
+        check(nrldpc_get_dims(h, &d));
+        need((int)mxGetM(prhs[2]) == d.N_cw, "cw_tilde should have N+2*Z_c rows.");
+        const int C = (int)mxGetN(prhs[2]);
+        check(nrldpc_set_llr_dtype(h, mxIsSingle(prhs[2]) ? NRLDPC_LLR_F32 : NRLDPC_LLR_F64));
+        const size_t NB8 = ((size_t)d.N_cw + 7) / 8;                   // bit-packed, as 'decode'
+        std::vector<uint8_t> packed(NB8 * (size_t)(C > 0 ? C : 1)), hard((size_t)d.K * (size_t)(C > 0 ? C : 1));
+        mxArray* unsat = mxCreateNumericMatrix(1, C, mxINT32_CLASS, mxREAL);
+        mxArray* it = mxCreateNumericMatrix(C, 1, mxINT32_CLASS, mxREAL);
+        nrldpc_cw_out o;
+        memset(&o, 0, sizeof o);
+        o.struct_size = sizeof o;
+        o.cw_packed = packed.data();
+        o.unsatisfied = (int32_t*)mxGetData(unsat);
+        check(nrldpc_decode_cw(h, mxGetData(prhs[2]), C, hard.data(), (int32_t*)mxGetData(it), &o));
+        plhs[0] = mxCreateLogicalMatrix(d.N_cw, C);                    // 'Whole codeword': (N+2*Z_c) x C logical
+        uint8_t* cw = (uint8_t*)mxGetData(plhs[0]);                    // mxLogical is one byte
+        for (int c = 0; c < C; ++c)
+            for (int v = 0; v < d.N_cw; ++v) cw[(size_t)c * d.N_cw + v] = (uint8_t)((packed[(size_t)c * NB8 + (v >> 3)] >> (v & 7)) & 1);
+        if (nlhs > 1) plhs[1] = unsat; else mxDestroyArray(unsat);
+        if (nlhs > 2) plhs[2] = it; else mxDestroyArray(it);
     } else if (!strcmp(cmd, "set_layers")) {
         need(nrhs == 3, "set_layers needs a handle and a layer count.");
         check(nrldpc_set_layers(handle_of(prhs[1]), (int32_t)mxGetScalar(prhs[2])));
