@@ -364,6 +364,44 @@ int nrldpc_awgn_llr_dev(const uint8_t* d_g, int64_t n_bits, int32_t Q_m, float E
  * are compared statistically).  Current HIP device.  (ABI revision 6.) */
 int nrldpc_payload_bits_dev(uint64_t seed, uint64_t first_block, int32_t n_tb, int32_t A, uint8_t* d_a, void* stream);
 
+/* The channel leg's two ends on their own, for a caller whose channel is not the library's (a capture, an equaliser's output, a
+ * fading model): the mirrors of NRModulator.m and NRDemodulator.m.  Stateless, current HIP device, asynchronous on `stream`.
+ * Added without a revision bump (a binding finds them by symbol); nothing an earlier caller uses changed.
+ *
+ * nrldpc_modulate_dev: d_g, n_bits bits (bytes {0,1}, the rate-matching stage's output), n_bits a multiple of Q_m in {1,2,4,6,8}
+ * -> d_tx, n_bits/Q_m symbols as interleaved float (re, im) pairs (complex64), unit average power.  Maps of NRModulator.m:73-81:
+ * BPSK +-e^{j pi/4}; QPSK and the QAMs one Gray-coded PAM rail per axis (TS 38.211 5.1.3-5.1.5), even bits on I, odd bits on Q,
+ * sign bit first, scaled by 1/sqrt(2 mean(level^2)).  Within two float roundings of the float64 map (tested: 4e-7 per component).
+ *
+ * nrldpc_demodulate_dev: d_rx, n_sym symbols (re, im) -> n_sym*Q_m values in d_out, by `method` (DecisionMethod, NRDemodulator.m:10):
+ *   NRLDPC_DEMOD_LLR         exact: per rail the log-sum-exp over its 2^(Q_m/2) levels, maximum subtracted -- the arithmetic of the
+ *                            fused kernel; LLR = log P(bit 0) - log P(bit 1), positive = bit 0, as everywhere in the library;
+ *   NRLDPC_DEMOD_APPROX_LLR  max-log: (min over the levels with bit 1 of d^2 - min over those with bit 0 of d^2) / N0; equal to the
+ *                            exact value for BPSK and QPSK (one level per bit value);
+ *   NRLDPC_DEMOD_HARD        bit = 1 exactly when the max-log LLR is < 0: the nearest constellation point, a tie gives 0 (so the
+ *                            sign bit of the max-log f32 LLR of the same input is the hard bit).  d_out: bytes {0,1}; out_dtype and the
+ *                            variance are not read.
+ * N0 is the complex noise variance (Variance, NRDemodulator.m:14,94-96): `variance` for every symbol, or, when d_variance is not
+ * null, d_variance[s] for symbol s (device, n_sym floats; replaces the scalar) -- equalised symbols, fading.  An array filled with
+ * one value gives the scalar call's bits.  Non-finite symbols and non-positive array entries: unspecified.
+ * out_dtype NRLDPC_LLR_F32 or NRLDPC_LLR_F16; an f16 LLR is clamped to +-65504 before conversion (a strong symbol must not become
+ * +inf, which the decoder reads as a filler bit: LLR conventions above).  Any address the element types allow and any n_sym >= 0
+ * are served, sub-ranges of a buffer included, and a call over a buffer equals calls over its parts bit for bit.
+ * Accuracy of both LLR methods against float64 (tests/test_modem_gpu.py, the fused kernel's operating points, BPSK -2 dB to
+ * 256QAM 45 dB): |dLLR| <= 5e-4 * max(1, |LLR|) for f32 (measured maximum: DESIGN.md section 4.12), plus 2^-11 |LLR| for f16.
+ * Errors, all before any device call: Q_m not in {1,2,4,6,8} ("Unsupported modulation", NRModulator.m:83), unknown method,
+ * out_dtype other than F32 / F16 -> NRLDPC_ERR_UNSUPPORTED; n_bits no multiple of Q_m, a negative size, a null pointer with a
+ * non-zero size, d_variance == NULL and `variance` not positive and finite -> NRLDPC_ERR_ARG.  A zero size returns NRLDPC_OK without
+ * a launch. */
+#define NRLDPC_DEMOD_LLR 0         /* 'Log-likelihood ratio'             (NRDemodulator.m:10) */
+#define NRLDPC_DEMOD_APPROX_LLR 1  /* 'Approximate log-likelihood ratio' */
+#define NRLDPC_DEMOD_HARD 2        /* 'Hard decision' */
+int nrldpc_modulate_dev(const uint8_t* d_g, int64_t n_bits, int32_t Q_m, float* d_tx /* [n_bits/Q_m][2] */, void* stream);
+int nrldpc_demodulate_dev(const float* d_rx /* [n_sym][2] */, int64_t n_sym, int32_t Q_m, int32_t method,
+                          float variance, const float* d_variance /* [n_sym], nullable */,
+                          void* d_out /* [n_sym*Q_m]: out_dtype for the two LLR methods, uint8 {0,1} for HARD */,
+                          int32_t out_dtype /* NRLDPC_LLR_F32 / _F16; not read for HARD */, void* stream);
+
 /* Kernel timing: when enabled, every *_dev / host call records HIP events around its kernel on the
  * launch stream; nrldpc_last_kernel_ms synchronises on the stop event and returns the duration. */
 int nrldpc_set_timing(nrldpc_handle h, int32_t enabled);

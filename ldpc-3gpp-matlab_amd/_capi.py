@@ -105,7 +105,8 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_pool_destroy", "nrldpc_pool_decode_dev", "nrldpc_pool_size", "nrldpc_abi_version", "nrldpc_decode_packed",
            "nrldpc_set_layers", "nrldpc_set_llr_dtype", "nrldpc_last_layers", "nrldpc_count_layers", "nrldpc_pool_set_layers", "nrldpc_pool_decode_packed",
            "nrldpc_decode_packed_layers", "nrldpc_pool_set_timing", "nrldpc_pool_last_kernel_ms", "nrldpc_last_host_phases", "nrldpc_payload_bits_dev",
-           "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm", "nrldpc_decode_cw", "nrldpc_decode_cw_dev"]
+           "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm", "nrldpc_decode_cw", "nrldpc_decode_cw_dev",
+           "nrldpc_modulate_dev", "nrldpc_demodulate_dev"]
 
 _lib = None
 
@@ -175,6 +176,8 @@ def load():
     L.nrldpc_crc_check_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp, vp, vp]
     L.nrldpc_crc_check_harq_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp, vp, vp, i32, vp]
     L.nrldpc_awgn_llr_dev.argtypes = [vp, C.c_int64, i32, C.c_float, C.c_uint64, C.c_uint64, vp, vp]
+    L.nrldpc_modulate_dev.argtypes = [vp, C.c_int64, i32, vp, vp]
+    L.nrldpc_demodulate_dev.argtypes = [vp, C.c_int64, i32, i32, C.c_float, vp, vp, i32, vp]
     L.nrldpc_crc_attach_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_rate_match_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_pool_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), i32, i32, C.POINTER(vp)]
@@ -556,6 +559,34 @@ def awgn_llr_dev(d_g, n_bits, Q_m, EsN0_dB, seed, first_symbol, d_g_tilde, strea
     """nrldpc_awgn_llr_dev: modulation + AWGN + exact LLRs in one kernel (plot_BLER_vs_SNR.m:130-132)."""
     check(load().nrldpc_awgn_llr_dev(_ptr(d_g), int(n_bits), int(Q_m), float(EsN0_dB), int(seed), int(first_symbol),
                                      _ptr(d_g_tilde), C.c_void_p(stream)))
+
+
+# NRLDPC_DEMOD_*: the three DecisionMethod values of the reference's NRDemodulator.m:10
+DEMOD_LLR, DEMOD_APPROX_LLR, DEMOD_HARD = 0, 1, 2
+DEMOD_METHODS = {"llr": DEMOD_LLR, "approx": DEMOD_APPROX_LLR, "hard": DEMOD_HARD,
+                 "Log-likelihood ratio": DEMOD_LLR, "Approximate log-likelihood ratio": DEMOD_APPROX_LLR, "Hard decision": DEMOD_HARD}
+
+
+def demod_method_code(method):
+    """NRLDPC_DEMOD_* of a method name ("llr" / "approx" / "hard" or the reference's DecisionMethod strings);
+    UnsupportedParameters for anything else (no device call)."""
+    try:
+        return DEMOD_METHODS[method]
+    except (KeyError, TypeError):
+        raise UnsupportedParameters("unknown decision method %r (one of %s)" % (method, ", ".join(DEMOD_METHODS))) from None
+
+
+def modulate_dev(d_g, n_bits, Q_m, d_tx, stream=0):
+    """nrldpc_modulate_dev: n_bits bit bytes at d_g -> n_bits / Q_m complex64 symbols at d_tx (NRModulator.m:73-81)."""
+    check(load().nrldpc_modulate_dev(_ptr(d_g), int(n_bits), int(Q_m), _ptr(d_tx), C.c_void_p(stream)))
+
+
+def demodulate_dev(d_rx, n_sym, Q_m, d_out, method="llr", variance=1.0, d_variance=None, out_dtype=LLR_F32, stream=0):
+    """nrldpc_demodulate_dev: n_sym complex64 symbols at d_rx -> n_sym * Q_m LLRs of out_dtype (LLR_F32 / LLR_F16; positive = bit 0)
+    at d_out, or hard-bit bytes for method "hard" (NRDemodulator.m:76-96).  variance: the complex noise variance N0;
+    d_variance: a device array of n_sym floats, one per symbol, that replaces it."""
+    check(load().nrldpc_demodulate_dev(_ptr(d_rx), int(n_sym), int(Q_m), demod_method_code(method), float(variance),
+                                       _ptr(d_variance), _ptr(d_out), int(out_dtype), C.c_void_p(stream)))
 
 
 def payload_bits_dev(seed, first_block, n_tb, A, d_a, stream=0):

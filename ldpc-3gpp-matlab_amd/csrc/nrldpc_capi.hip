@@ -35,6 +35,7 @@
 #include "nrldpc_sched.h"
 #include "nrldpc_bp.h"
 #include "nrldpc_cwout.h"
+#include "nrldpc_modem.h"
 
 static_assert(sizeof(nrldpc_cw_out) == 32, "nrldpc_cw_out: the size include/nrldpc.h states");
 
@@ -2003,6 +2004,42 @@ int nrldpc_awgn_llr_dev(const uint8_t* d_g, int64_t n_bits, int32_t Q_m, float E
     a.inv_norm = (float)(1.0 / std::sqrt(2.0 * mean_sq[Q_m / 2]));
     hipError_t e = nrldpc::launch_awgn_llr(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hipfail(e, "channel kernel launch");
+    return NRLDPC_OK;
+}
+
+// ---- stand-alone mapper / demapper (nrldpc_modem.hip): every check before any device call ----
+static const double kRailMeanSq[5] = {1.0, 1.0, 5.0, 21.0, 85.0}; // mean(level^2) of a rail with 0,1,2,3,4 bits
+
+int nrldpc_modulate_dev(const uint8_t* d_g, int64_t n_bits, int32_t Q_m, float* d_tx, void* stream) {
+    if (Q_m != 1 && Q_m != 2 && Q_m != 4 && Q_m != 6 && Q_m != 8) return fail(NRLDPC_ERR_UNSUPPORTED, "Unsupported modulation");
+    if (n_bits < 0 || n_bits % Q_m) return fail(NRLDPC_ERR_ARG, "n_bits must be a non-negative multiple of Q_m");
+    if (n_bits == 0) return NRLDPC_OK;
+    if (!d_g || !d_tx) return fail(NRLDPC_ERR_ARG, "null pointer");
+    nrldpc::ModArgs a;
+    a.g = d_g; a.tx = d_tx; a.n_sym = n_bits / Q_m; a.Qm = Q_m;
+    a.inv_norm = (float)(1.0 / std::sqrt(2.0 * kRailMeanSq[Q_m / 2]));
+    hipError_t e = nrldpc::launch_modulate(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mapper kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_demodulate_dev(const float* d_rx, int64_t n_sym, int32_t Q_m, int32_t method, float variance, const float* d_variance,
+                          void* d_out, int32_t out_dtype, void* stream) {
+    if (Q_m != 1 && Q_m != 2 && Q_m != 4 && Q_m != 6 && Q_m != 8) return fail(NRLDPC_ERR_UNSUPPORTED, "Unsupported modulation");
+    if (method != NRLDPC_DEMOD_LLR && method != NRLDPC_DEMOD_APPROX_LLR && method != NRLDPC_DEMOD_HARD)
+        return fail(NRLDPC_ERR_UNSUPPORTED, "unknown decision method");
+    const bool hard = method == NRLDPC_DEMOD_HARD;
+    if (!hard && out_dtype != NRLDPC_LLR_F32 && out_dtype != NRLDPC_LLR_F16) return fail(NRLDPC_ERR_UNSUPPORTED, "out_dtype must be f32 or f16");
+    if (n_sym < 0) return fail(NRLDPC_ERR_ARG, "negative symbol count");
+    if (n_sym > 0 && (!d_rx || !d_out)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (!d_variance && !(variance > 0.0f && std::isfinite(variance))) return fail(NRLDPC_ERR_ARG, "variance must be positive and finite");
+    if (n_sym == 0) return NRLDPC_OK;
+    nrldpc::DemodArgs a;
+    a.rx = d_rx; a.var = d_variance; a.out = d_out; a.n_sym = n_sym; a.Qm = Q_m; a.method = method; a.out_dtype = out_dtype;
+    a.variance = d_variance ? 1.0f : variance;
+    a.inv_norm = (float)(1.0 / std::sqrt(2.0 * kRailMeanSq[Q_m / 2]));
+    hipError_t e = nrldpc::launch_demodulate(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "demapper kernel launch");
     return NRLDPC_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "nrldpc_kernels.h"
+#include "nrldpc_modem.h"
 
 namespace nrldpc {
 
@@ -29,48 +30,7 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
 }
 
-// amplitude of one I/Q rail from its NB bits, most significant (sign) first: TS 38.211 5.1.3-5.1.5,
-// 16QAM (1-2b0)(2-(1-2b2)), 64QAM (1-2b0)(4-(1-2b2)(2-(1-2b4))), 256QAM one level more
-template <int NB> __device__ __forceinline__ float pam_level(uint32_t code) {
-    float x = 1.0f;
-#pragma unroll
-    for (int j = 1; j < NB; ++j) {
-        const uint32_t b = (code >> (j - 1)) & 1u; // innermost (last) bit first
-        x = (float)(1 << j) - (b ? -x : x);
-    }
-    return ((code >> (NB - 1)) & 1u) ? -x : x;
-}
-
-template <int NB> __device__ __forceinline__ void rail_llr(float y, float inv_n0, float inv_norm, float (&llr)[NB]) {
-    if constexpr (NB == 1) { // two points +-p: log-sum-exp of one term each, ((y+p)^2 - (y-p)^2)/N0 = 4 p y / N0
-        llr[0] = 4.0f * inv_norm * y * inv_n0;
-        return;
-    }
-    float mx[NB][2], sm[NB][2];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) { mx[k][0] = mx[k][1] = -3.0e38f; sm[k][0] = sm[k][1] = 0.0f; }
-    float met[1 << NB];
-#pragma unroll
-    for (uint32_t c = 0; c < (1u << NB); ++c) {
-        const float d = y - pam_level<NB>(c) * inv_norm;
-        met[c] = -d * d * inv_n0;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            const int bit = (c >> (NB - 1 - k)) & 1u;
-            mx[k][bit] = fmaxf(mx[k][bit], met[c]);
-        }
-    }
-#pragma unroll
-    for (uint32_t c = 0; c < (1u << NB); ++c)
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            const int bit = (c >> (NB - 1 - k)) & 1u;
-            sm[k][bit] += __builtin_amdgcn_exp2f((met[c] - mx[k][bit]) * 1.4426950408889634f); // e^x = 2^(x log2 e): v_exp_f32
-        }
-#pragma unroll
-    for (int k = 0; k < NB; ++k) // (sums lie in [1, 2^NB]: v_log_f32 needs no denormal care)
-        llr[k] = (mx[k][0] - mx[k][1]) + 0.6931471805599453f * (__builtin_amdgcn_logf(sm[k][0]) - __builtin_amdgcn_logf(sm[k][1]));
-}
+// pam_level<NB> / rail_llr<NB>, the rail arithmetic: nrldpc_modem.h (shared with the stand-alone demapper)
 
 // LLRs of one symbol from its bits and the two uniform words of its noise sample
 template <int QM> __device__ __forceinline__ void symbol_llr(const ChanArgs& a, const uint8_t* g, uint32_t w1, uint32_t w2, float* o) {

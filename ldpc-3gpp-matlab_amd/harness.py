@@ -149,7 +149,7 @@ def payload_bits(seed, first_block, n, A, dev):
 ATTEMPT_STRIDE = 1 << 40  # Philox symbol counter = attempt * 2^40 + global block index * symbols per block + symbol
 
 
-def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_block):
+def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_block, channel=None):
     """simulate_point with every stage on the GPU(s) (rows N1-N4 of SURVEY.md section 8f): payload, CRC attachment,
     encoding, rate matching, modulation + AWGN + exact LLRs (one HIP kernel, nrldpc_awgn_llr_dev), rate recovery, decoding,
     CRC check, error count.
@@ -160,9 +160,15 @@ def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_
     the outcome vector -- and the result file plot_BLER_vs_SNR writes from it -- is identical for 1, 2, 4 or 8 shards:
     the reference's "parallel instances ... aggregated together" (plot_BLER_vs_SNR.m:23-27) without the manual step,
     and without any collective (transport blocks are independent).  Work of all shards is launched before the first
-    synchronisation, so GPUs run concurrently under one host thread."""
+    synchronisation, so GPUs run concurrently under one host thread.
+
+    channel: None -- the fused kernel and its own AWGN -- or a callable channel(tx, N0, first_symbol) for a channel of the caller's:
+    tx is the step's complex64 device tensor [n][G / Q_m] of unit-power symbols, N0 the noise variance of the SNR point,
+    first_symbol the global index of tx's first symbol (what the fused kernel counts its noise by); it returns the received
+    symbols, same shape and type, on the same device and stream.  :130-132 then run as three steps, nrldpc_modulate_dev ->
+    channel -> nrldpc_demodulate_dev (exact LLRs, Variance = N0); nothing else in the loop changes."""
     import torch
-    from ._capi import awgn_llr_dev
+    from ._capi import awgn_llr_dev, demodulate_dev, modulate_dev
     D = len(chains)
     cuts = [shard_range(batch, d, D)[0] for d in range(D)] + [batch]   # contiguous slices (shard.py), as every multi-GPU path here
     N0 = 1.0 / 10.0 ** (EsN0 / 10.0)
@@ -187,8 +193,16 @@ def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_
                 g = enc_chain.step(s["a"])
                 g_tilde = torch.empty(g.shape, dtype=torch.float32, device=dev)           # :130-132 in one kernel
                 first_symbol = n_rv * ATTEMPT_STRIDE + (first_block + cuts[d]) * (p.G // Q_m)
-                awgn_llr_dev(g.data_ptr(), g.numel(), Q_m, EsN0, seed, first_symbol, g_tilde.data_ptr(),
-                             torch.cuda.current_stream(dev).cuda_stream)
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                if channel is None:
+                    awgn_llr_dev(g.data_ptr(), g.numel(), Q_m, EsN0, seed, first_symbol, g_tilde.data_ptr(), stream)
+                else:
+                    tx = torch.empty(g.shape[:-1] + (g.shape[-1] // Q_m,), dtype=torch.complex64, device=dev)
+                    modulate_dev(g.data_ptr(), g.numel(), Q_m, tx.data_ptr(), stream)                       # :130
+                    rx = channel(tx, N0, first_symbol).to(torch.complex64).contiguous()                     # :131
+                    if rx.shape != tx.shape or rx.device != tx.device:
+                        raise ValueError("channel() should return a device tensor shaped like its input")
+                    demodulate_dev(rx.data_ptr(), rx.numel(), Q_m, g_tilde.data_ptr(), method="llr", variance=N0, stream=stream)  # :132
                 dec, good, _ = dec_chain.step(g_tilde)
                 newly = good & ~s["ok"]
                 s["a_hat"] = torch.where(newly[:, None], dec, s["a_hat"])  # (no boolean indexing: a host sync per batch)
@@ -258,8 +272,9 @@ def simulate_point(hEnc, hDec, Q_m, EsN0, rv_id_sequence, batch, rng):
 
 def plot_BLER_vs_SNR(A=3842, R=1 / 3, BG=2, Modulation="QPSK", rv_id_sequence=(0,), iterations=8,
                      target_block_errors=3, target_BLER=1e-3, EsN0_start=0.0, EsN0_delta=0.5, seed=0,
-                     results_dir="results", batch=256, max_points=200, decoder_kwargs=None, device=False, devices=None):
+                     results_dir="results", batch=256, max_points=200, decoder_kwargs=None, device=False, devices=None, channel=None):
     """Same positional parameters and defaults as plot_BLER_vs_SNR.m:1,30-42 (no figure is drawn).
+    channel: with device=True, the caller's channel in place of the fused kernel's AWGN (simulate_point_device).
     device=True keeps every stage on the GPU (simulate_point_device); devices = HIP ordinals of the shards (default [0];
     an ordinal may repeat: logical shards on one GPU) -- the result file does not depend on their number.
     Returns {(A, R, BG): [(EsN0, BLER, blocks), ...]}."""
@@ -302,7 +317,8 @@ def plot_BLER_vs_SNR(A=3842, R=1 / 3, BG=2, Modulation="QPSK", rv_id_sequence=(0
                             keep_going = True
                             while keep_going and errors < target_block_errors:                           # :116
                                 if device:
-                                    outcomes = simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, curve_seed, first_block)
+                                    outcomes = simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, curve_seed, first_block,
+                                                                     channel=channel)
                                     first_block += batch
                                 else:
                                     outcomes = simulate_point(hEnc, hDec, Q_m, EsN0, rv_id_sequence, batch, rng)
