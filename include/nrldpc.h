@@ -317,9 +317,34 @@ typedef struct nrldpc_tb_params {
 /* Rate recovery: replaces code_block_concatenation + bit_interleaving + bit_selection (NRLDPCDecoder.m:143-242)
  * and the 2Z-zero prefix / NaN->+inf of LDPC_coding (:262-264).  d_g_tilde: [n_tb][G] f32 LLRs.
  * d_harq (nullable = I_HARQ 0): [n_tb][C][N_cb] f32 soft buffer, accumulated in place (:236-239).
- * d_cw_llr: [n_tb*C][ncols*Z] of out_dtype (NRLDPC_LLR_F32 / _F16): the decoder core's input. */
+ * d_cw_llr: [n_tb*C][ncols*Z] of out_dtype (NRLDPC_LLR_F32 / _F16): the decoder core's input.
+ * For f16 demodulator LLRs or an f16 soft buffer see nrldpc_rate_recover_ex_dev below. */
 int nrldpc_rate_recover_dev(const nrldpc_tb_params* p, const float* d_g_tilde, int32_t n_tb, float* d_harq,
                             void* d_cw_llr, int32_t out_dtype, void* stream);
+
+/* The same stage with the element type of every array chosen per call: in_dtype (d_g_tilde), harq_dtype (d_harq; not read when
+ * d_harq is null) and out_dtype (d_cw_llr) each take NRLDPC_LLR_F32 or NRLDPC_LLR_F16.  Added without a revision bump
+ * (NRLDPC_ABI_VERSION stays 6): a binding finds it by symbol.  nrldpc_rate_recover_dev itself is unchanged.
+ *   f16 input   is widened to f32, which is exact; the same sums then run in the same order as in nrldpc_rate_recover_dev:
+ *               repetitions in ascending k, then the buffer.
+ *   f16 buffer  for a non-filler position p inside the circular buffer: val = (f32 sum of what this transmission delivers to p) +
+ *               float(buffer[p]), one f32 add; buffer[p] = half(clamp(val, +-65504)), round to nearest even; the decoder's LLR at p
+ *               is the stored value widened.  The decoder always sees exactly what the buffer holds, so a later call that delivers
+ *               nothing to p reproduces it.  Filler positions of the buffer are never touched; their output is +inf, as ever.
+ *   clamp rule  this entry point clamps a finite value to +-65504 before ANY conversion to f16, for the buffer and for the output --
+ *               the demapper's rule for the same reason: +inf means "filler bit, known 0" to the decoder, and soft combining over
+ *               retransmissions is where magnitudes grow.  With (in_dtype, harq_dtype) = (F32, F32) the call equals
+ *               nrldpc_rate_recover_dev bit for bit, buffer included, wherever that call's output is finite or a filler; where that
+ *               call overflows an f16 output to +-inf, this one gives +-65504.
+ *   addresses   any address the element types allow is served: an f16 array may sit at an odd multiple of 2 bytes (rows of
+ *               d_g_tilde do when G is odd, rows of the buffer when N_cb is odd -- limited-buffer rate matching), and a sub-range
+ *               of a larger allocation works.
+ *   Non-finite input LLRs: unspecified (the demapper never produces them).
+ * Errors, all before any device call: a dtype other than F32 / F16 -> NRLDPC_ERR_UNSUPPORTED; null p, negative n_tb, null d_cw_llr
+ * or null d_g_tilde (with G > 0) when n_tb > 0 -> NRLDPC_ERR_ARG; the parameter checks of nrldpc_rate_recover_dev with the same
+ * texts.  n_tb == 0 returns NRLDPC_OK without a launch. */
+int nrldpc_rate_recover_ex_dev(const nrldpc_tb_params* p, const void* d_g_tilde, int32_t in_dtype, int32_t n_tb,
+                               void* d_harq, int32_t harq_dtype, void* d_cw_llr, int32_t out_dtype, void* stream);
 
 /* CRC stages: replaces code_block_segmentation + crc_calculation of the decoder (NRLDPCDecoder.m:271-340).
  * d_c_hat: [n_tb*C][K] hard bits from nrldpc_decode_dev.  d_b_hat: [n_tb][B] bytes (a_hat = first A of a row).

@@ -106,7 +106,7 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_set_layers", "nrldpc_set_llr_dtype", "nrldpc_last_layers", "nrldpc_count_layers", "nrldpc_pool_set_layers", "nrldpc_pool_decode_packed",
            "nrldpc_decode_packed_layers", "nrldpc_pool_set_timing", "nrldpc_pool_last_kernel_ms", "nrldpc_last_host_phases", "nrldpc_payload_bits_dev",
            "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm", "nrldpc_decode_cw", "nrldpc_decode_cw_dev",
-           "nrldpc_modulate_dev", "nrldpc_demodulate_dev"]
+           "nrldpc_modulate_dev", "nrldpc_demodulate_dev", "nrldpc_rate_recover_ex_dev"]
 
 _lib = None
 
@@ -173,6 +173,8 @@ def load():
     L.nrldpc_encode.argtypes = [vp, vp, i32, vp]
     L.nrldpc_encode_dev.argtypes = [vp, vp, i32, vp, vp]
     L.nrldpc_rate_recover_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp, i32, vp]
+    if hasattr(L, "nrldpc_rate_recover_ex_dev"):  # added without a revision bump: a library selected with NRLDPC_LIB may lack it
+        L.nrldpc_rate_recover_ex_dev.argtypes = [C.POINTER(TbParams), vp, i32, i32, vp, i32, vp, i32, vp]
     L.nrldpc_crc_check_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp, vp, vp]
     L.nrldpc_crc_check_harq_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp, vp, vp, i32, vp]
     L.nrldpc_awgn_llr_dev.argtypes = [vp, C.c_int64, i32, C.c_float, C.c_uint64, C.c_uint64, vp, vp]
@@ -530,11 +532,21 @@ def decode_multi_dev(codecs, d_llr, batch, d_hard, d_iters=None, stream=0):
     MultiCall(codecs, d_llr, batch, d_hard, d_iters)(stream)
 
 
-def rate_recover_dev(p, d_g_tilde, n_tb, d_harq, d_cw_llr, out_dtype=LLR_F32, stream=0):
-    """nrldpc_rate_recover_dev on raw device addresses (p: NRLDPC parameter object or TbParams)."""
+def rate_recover_dev(p, d_g_tilde, n_tb, d_harq, d_cw_llr, out_dtype=LLR_F32, stream=0, in_dtype=LLR_F32, harq_dtype=LLR_F32):
+    """nrldpc_rate_recover_dev on raw device addresses (p: NRLDPC parameter object or TbParams).  in_dtype / harq_dtype: the element
+    types at d_g_tilde and d_harq (LLR_F32 / LLR_F16); anything but f32 for both goes to nrldpc_rate_recover_ex_dev, which also
+    clamps what it converts to f16 (include/nrldpc.h)."""
     t = p if isinstance(p, TbParams) else tb_params(p)
-    check(load().nrldpc_rate_recover_dev(C.byref(t), _ptr(d_g_tilde), int(n_tb), _ptr(d_harq), _ptr(d_cw_llr),
-                                         int(out_dtype), C.c_void_p(stream)))
+    L = load()
+    if int(in_dtype) == LLR_F32 and (d_harq is None or int(harq_dtype) == LLR_F32):
+        check(L.nrldpc_rate_recover_dev(C.byref(t), _ptr(d_g_tilde), int(n_tb), _ptr(d_harq), _ptr(d_cw_llr),
+                                        int(out_dtype), C.c_void_p(stream)))
+        return
+    if not hasattr(L, "nrldpc_rate_recover_ex_dev"):
+        raise NRLDPCError("%s has no nrldpc_rate_recover_ex_dev: f16 demodulator LLRs and the f16 HARQ buffer need a library "
+                          "built from this tree (NRLDPC_LIB selects an older one?)" % lib_path())
+    check(L.nrldpc_rate_recover_ex_dev(C.byref(t), _ptr(d_g_tilde), int(in_dtype), int(n_tb), _ptr(d_harq), int(harq_dtype),
+                                       _ptr(d_cw_llr), int(out_dtype), C.c_void_p(stream)))
 
 
 def crc_check_dev(p, d_c_hat, n_tb, d_b_hat, d_ok, d_cb_pass=None, stream=0):

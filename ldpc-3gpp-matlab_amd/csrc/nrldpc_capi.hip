@@ -36,6 +36,7 @@
 #include "nrldpc_bp.h"
 #include "nrldpc_cwout.h"
 #include "nrldpc_modem.h"
+#include "nrldpc_ratematch_ex.h"
 
 static_assert(sizeof(nrldpc_cw_out) == 32, "nrldpc_cw_out: the size include/nrldpc.h states");
 
@@ -706,6 +707,19 @@ int encode_launch(nrldpc_codec* h, const uint8_t* d_info, int batch, uint8_t* d_
     hipError_t e = nrldpc::launch_encode(a, stream);
     end_timing(h, stream);
     if (e != hipSuccess) return hipfail(e, "encode kernel launch");
+    return NRLDPC_OK;
+}
+
+// the per-code-block part of the rate-recovery arguments (RmArgs / RmExArgs: the same fields under the same names)
+template <class A> int fill_rm_blocks(const nrldpc_tb_params* p, int32_t n_tb, A& a) {
+    a.n_tb = n_tb; a.C = p->C; a.G = p->G; a.Z = p->Z; a.K = p->K; a.Kp = p->K_prime; a.N = p->N; a.N_cb = p->N_cb;
+    a.k0 = p->k_0; a.Qm = p->Q_m;
+    int off = 0;
+    for (int r = 0; r < p->C; ++r) {
+        if (p->E_r[r] < 0 || p->E_r[r] % p->Q_m) return fail(NRLDPC_ERR_UNSUPPORTED, "E_r must be a non-negative multiple of Q_m");
+        a.E[r] = p->E_r[r]; a.off[r] = off; off += p->E_r[r];
+    }
+    if (off != p->G) return fail(NRLDPC_ERR_ARG, "sum(E_r) must equal G");
     return NRLDPC_OK;
 }
 
@@ -1883,15 +1897,7 @@ static int make_rm_args(const nrldpc_tb_params* p, const float* d_g_tilde, int32
     nrldpc::RmArgs& a = *out;
     memset(&a, 0, sizeof a);
     a.g = d_g_tilde; a.harq = d_harq; a.out = d_cw_llr; a.out_f16 = out_dtype == NRLDPC_LLR_F16;
-    a.n_tb = n_tb; a.C = p->C; a.G = p->G; a.Z = p->Z; a.K = p->K; a.Kp = p->K_prime; a.N = p->N; a.N_cb = p->N_cb;
-    a.k0 = p->k_0; a.Qm = p->Q_m;
-    int off = 0;
-    for (int r = 0; r < p->C; ++r) {
-        if (p->E_r[r] < 0 || p->E_r[r] % p->Q_m) return fail(NRLDPC_ERR_UNSUPPORTED, "E_r must be a non-negative multiple of Q_m");
-        a.E[r] = p->E_r[r]; a.off[r] = off; off += p->E_r[r];
-    }
-    if (off != p->G) return fail(NRLDPC_ERR_ARG, "sum(E_r) must equal G");
-    return NRLDPC_OK;
+    return fill_rm_blocks(p, n_tb, a);
 }
 
 int nrldpc_rate_recover_dev(const nrldpc_tb_params* p, const float* d_g_tilde, int32_t n_tb, float* d_harq,
@@ -1906,6 +1912,29 @@ int nrldpc_rate_recover_dev(const nrldpc_tb_params* p, const float* d_g_tilde, i
     rc = make_rm_args(p, d_g_tilde, n_tb, d_harq, d_cw_llr, out_dtype, &a);
     if (rc) return rc;
     hipError_t e = nrldpc::launch_rate_recover(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "rate-recovery kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_rate_recover_ex_dev(const nrldpc_tb_params* p, const void* d_g_tilde, int32_t in_dtype, int32_t n_tb,
+                               void* d_harq, int32_t harq_dtype, void* d_cw_llr, int32_t out_dtype, void* stream) {
+    static_assert(nrldpc::RMX_MAX_C == NRLDPC_MAX_C, "RmExArgs holds one entry per code block");
+    int rc = check_tb_params(p);
+    if (rc) return rc;
+    auto known = [](int32_t d) { return d == NRLDPC_LLR_F32 || d == NRLDPC_LLR_F16; };
+    if (!known(in_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "in_dtype must be f32 or f16");
+    if (d_harq && !known(harq_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "harq_dtype must be f32 or f16");
+    if (!known(out_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "out_dtype must be f32 or f16");
+    if (n_tb < 0) return fail(NRLDPC_ERR_ARG, "negative batch");
+    if (n_tb == 0) return NRLDPC_OK;
+    if (!d_cw_llr || (!d_g_tilde && p->G > 0)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    nrldpc::RmExArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = d_g_tilde; a.harq = d_harq; a.out = d_cw_llr;
+    a.in_f16 = in_dtype == NRLDPC_LLR_F16; a.harq_f16 = d_harq && harq_dtype == NRLDPC_LLR_F16; a.out_f16 = out_dtype == NRLDPC_LLR_F16;
+    rc = fill_rm_blocks(p, n_tb, a);
+    if (rc) return rc;
+    hipError_t e = nrldpc::launch_rate_recover_ex(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hipfail(e, "rate-recovery kernel launch");
     return NRLDPC_OK;
 }

@@ -6,7 +6,7 @@ with no host loop and no PCIe traffic in between.  torch is used for device memo
 """
 import numpy as np
 
-from ._capi import LLR_F16, LLR_F32, Codec, NRLDPCError, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
+from ._capi import LLR_F16, LLR_F32, Codec, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
 from .nrldpc import NRLDPC
 
 
@@ -38,10 +38,18 @@ class DeviceDecodeChain:
     code_block_CRC_passed flags (`cb_pass`); reset() clears them (:343-356).  CBGTI of `params` is honoured (:304)."""
 
     def __init__(self, params: NRLDPC, iterations=50, I_HARQ=0, alpha=None, llr_scale=0, prune_layers=True,
-                 llr_dtype=None, device_id=0, beta=0.0, crc_stop=False, algorithm="min-sum"):
+                 llr_dtype=None, device_id=0, beta=0.0, crc_stop=False, algorithm="min-sum", harq_dtype=None):
         """llr_dtype: of the LLRs rate recovery hands the decoder; None = fp16 for "min-sum" (its kernels quantise to an int8 grid
-        anyway), f32 for "sum-product" (flooding sum-product, the reference's comm.LDPCDecoder: it ingests the values unquantised)."""
+        anyway), f32 for "sum-product" (flooding sum-product, the reference's comm.LDPCDecoder: it ingests the values unquantised).
+        harq_dtype: of the soft buffer (only with I_HARQ): None / np.float32 = the reference's accumulation in f32, np.float16 = half
+        the memory; the buffer then saturates at +-65504 and the decoder sees exactly what it holds (nrldpc_rate_recover_ex_dev)."""
         algorithm_code(algorithm)  # UnsupportedParameters for an unknown name, before any device work
+        try:
+            self.harq_dtype = np.dtype(np.float32 if harq_dtype is None else harq_dtype)
+        except TypeError:
+            self.harq_dtype = None
+        if self.harq_dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+            raise UnsupportedParameters("harq_dtype should be numpy float32 or float16, not %r." % (harq_dtype,))
         import torch
         self.torch = torch
         params.validate()
@@ -86,11 +94,11 @@ class DeviceDecodeChain:
         return self._codec
 
     def step(self, g_tilde):
-        """g_tilde: torch float32 tensor [n_tb][G] on the device (positive = bit 0).
+        """g_tilde: torch float32 or float16 tensor [n_tb][G] on the device (positive = bit 0).
         Returns (a_hat uint8 [n_tb][A], ok bool [n_tb], iters int32 [n_tb][C]) as device tensors."""
         torch, p = self.torch, self.p
-        if g_tilde.dim() != 2 or g_tilde.shape[1] != p.G or g_tilde.dtype != torch.float32 or not g_tilde.is_cuda:
-            raise NRLDPCError("g_tilde should be a float32 device tensor of shape [n_tb][G].")
+        if g_tilde.dim() != 2 or g_tilde.shape[1] != p.G or g_tilde.dtype not in (torch.float32, torch.float16) or not g_tilde.is_cuda:
+            raise NRLDPCError("g_tilde should be a float32 or float16 device tensor of shape [n_tb][G].")
         if g_tilde.device != self.dev:
             raise NRLDPCError("g_tilde lives on %s, this chain on %s." % (g_tilde.device, self.dev))
         with torch.cuda.device(self.dev):  # the stateless stage kernels launch on the current HIP device
@@ -119,11 +127,13 @@ class DeviceDecodeChain:
             self.cb_pass = torch.zeros((n_tb, C_), dtype=torch.int32, device=self.dev)
             self.b_hat = torch.zeros((n_tb, d.B), dtype=torch.uint8, device=self.dev)
             if self.I_HARQ:
-                self.harq = torch.zeros((n_tb, C_, d.N_cb), dtype=torch.float32, device=self.dev)
+                self.harq = torch.zeros((n_tb, C_, d.N_cb), dtype=torch.float16 if self.harq_dtype == np.float16 else torch.float32, device=self.dev)
         tdt = torch.float16 if self.llr_dtype == np.float16 else torch.float32
         cw_llr = torch.empty((n_tb * C_, ncwz), dtype=tdt, device=self.dev)
         rate_recover_dev(t, g_tilde.data_ptr(), n_tb, self.harq.data_ptr() if self.I_HARQ else None,
-                         cw_llr.data_ptr(), LLR_F16 if tdt == torch.float16 else LLR_F32, stream)
+                         cw_llr.data_ptr(), LLR_F16 if tdt == torch.float16 else LLR_F32, stream,
+                         in_dtype=LLR_F16 if g_tilde.dtype == torch.float16 else LLR_F32,
+                         harq_dtype=LLR_F16 if self.harq_dtype == np.float16 else LLR_F32)
         rows = 46 if d.BG == 1 else 42
         n_layers = rows
         if self.prune:

@@ -149,7 +149,7 @@ def payload_bits(seed, first_block, n, A, dev):
 ATTEMPT_STRIDE = 1 << 40  # Philox symbol counter = attempt * 2^40 + global block index * symbols per block + symbol
 
 
-def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_block, channel=None):
+def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_block, channel=None, llr_dtype=None):
     """simulate_point with every stage on the GPU(s) (rows N1-N4 of SURVEY.md section 8f): payload, CRC attachment,
     encoding, rate matching, modulation + AWGN + exact LLRs (one HIP kernel, nrldpc_awgn_llr_dev), rate recovery, decoding,
     CRC check, error count.
@@ -166,9 +166,17 @@ def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_
     tx is the step's complex64 device tensor [n][G / Q_m] of unit-power symbols, N0 the noise variance of the SNR point,
     first_symbol the global index of tx's first symbol (what the fused kernel counts its noise by); it returns the received
     symbols, same shape and type, on the same device and stream.  :130-132 then run as three steps, nrldpc_modulate_dev ->
-    channel -> nrldpc_demodulate_dev (exact LLRs, Variance = N0); nothing else in the loop changes."""
+    channel -> nrldpc_demodulate_dev (exact LLRs, Variance = N0); nothing else in the loop changes.
+
+    llr_dtype: None / np.float32, or np.float16 -- with a channel of the caller's the demapper then writes f16 LLRs and the decode
+    chain is stepped with them as they are (no f32 copy of g_tilde exists).  The fused kernel writes f32 only: not read without
+    `channel`."""
     import torch
-    from ._capi import awgn_llr_dev, demodulate_dev, modulate_dev
+    from ._capi import LLR_F16, LLR_F32, UnsupportedParameters, awgn_llr_dev, demodulate_dev, modulate_dev
+    llr_dt = np.dtype(np.float32 if llr_dtype is None else llr_dtype)
+    if llr_dt not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise UnsupportedParameters("llr_dtype should be numpy float32 or float16, not %r." % (llr_dtype,))
+    half = channel is not None and llr_dt == np.float16
     D = len(chains)
     cuts = [shard_range(batch, d, D)[0] for d in range(D)] + [batch]   # contiguous slices (shard.py), as every multi-GPU path here
     N0 = 1.0 / 10.0 ** (EsN0 / 10.0)
@@ -191,7 +199,7 @@ def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_
             p.rv_id = rv
             with torch.cuda.device(dev):
                 g = enc_chain.step(s["a"])
-                g_tilde = torch.empty(g.shape, dtype=torch.float32, device=dev)           # :130-132 in one kernel
+                g_tilde = torch.empty(g.shape, dtype=torch.float16 if half else torch.float32, device=dev)  # :130-132 in one kernel
                 first_symbol = n_rv * ATTEMPT_STRIDE + (first_block + cuts[d]) * (p.G // Q_m)
                 stream = torch.cuda.current_stream(dev).cuda_stream
                 if channel is None:
@@ -202,7 +210,8 @@ def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_
                     rx = channel(tx, N0, first_symbol).to(torch.complex64).contiguous()                     # :131
                     if rx.shape != tx.shape or rx.device != tx.device:
                         raise ValueError("channel() should return a device tensor shaped like its input")
-                    demodulate_dev(rx.data_ptr(), rx.numel(), Q_m, g_tilde.data_ptr(), method="llr", variance=N0, stream=stream)  # :132
+                    demodulate_dev(rx.data_ptr(), rx.numel(), Q_m, g_tilde.data_ptr(), method="llr", variance=N0,
+                                   out_dtype=LLR_F16 if half else LLR_F32, stream=stream)                   # :132
                 dec, good, _ = dec_chain.step(g_tilde)
                 newly = good & ~s["ok"]
                 s["a_hat"] = torch.where(newly[:, None], dec, s["a_hat"])  # (no boolean indexing: a host sync per batch)
