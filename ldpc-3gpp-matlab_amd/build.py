@@ -22,12 +22,19 @@ ALLMODES = bool(os.environ.get("NRLDPC_BUILD_ALLMODES"))
 # NRLDPC_BUILD_EXTRA_FLAGS="<flags>": the experiment build with extra compiler flags for every unit (e.g. LLVM scheduling options), into its
 # own library and object directory (libnrldpc_hip_x.so, build_x/); load it with NRLDPC_LIB=<path>
 XFLAGS = os.environ.get("NRLDPC_BUILD_EXTRA_FLAGS", "").split()
-LIB = os.environ.get("NRLDPC_LIB") or os.path.join(HERE, "libnrldpc_hip_ab.so" if AB else "libnrldpc_hip_allmodes.so" if ALLMODES else "libnrldpc_hip_x.so" if XFLAGS else "libnrldpc_hip.so")  # env override: kernel experiments
-OBJDIR = os.path.join(HERE, "build_ab" if AB else "build_allmodes" if ALLMODES else "build_x" if XFLAGS else "build")
+# NRLDPC_BUILD_NOPAIR=1: the A/B build in which every unit of Z64_PAIR compiles from the plain instantiation file (the one-edge-at-a-time
+# two-smallest search) -- its own library and object directory (libnrldpc_hip_nopair.so, build_nopair/; seed the directory with a copy of
+# build/: only the units of Z64_PAIR recompile); load it with NRLDPC_LIB=<path>
+NOPAIR = bool(os.environ.get("NRLDPC_BUILD_NOPAIR"))
+LIB = os.environ.get("NRLDPC_LIB") or os.path.join(HERE, "libnrldpc_hip_ab.so" if AB else "libnrldpc_hip_allmodes.so" if ALLMODES else "libnrldpc_hip_x.so" if XFLAGS else "libnrldpc_hip_nopair.so" if NOPAIR else "libnrldpc_hip.so")  # env override: kernel experiments
+OBJDIR = os.path.join(HERE, "build_ab" if AB else "build_allmodes" if ALLMODES else "build_x" if XFLAGS else "build_nopair" if NOPAIR else "build")
 SOURCES = ["nrldpc_decode.hip", "nrldpc_encode.hip", "nrldpc_ratematch.hip", "nrldpc_crc.hip", "nrldpc_channel.hip",
            "nrldpc_expand.hip", "nrldpc_decode_bp.hip", "nrldpc_cwout.hip", "nrldpc_modem.hip", "nrldpc_ratematch_ex.hip", "nrldpc_capi.hip", "nrldpc_host_quant.cpp"]  # .cpp: host-only C++ (no device pass)
 Z64_SOURCE = "nrldpc_decode_z64_inst.hip"
 Z64P_SOURCE = "nrldpc_decode_z64p_inst.hip"
+# the same instantiation with the split form's two-smallest search over pairs of edges (nrldpc_decode_z64_pair.h)
+Z64Q_SOURCE = "nrldpc_decode_z64q_inst.hip"
+Z64Q_HEADER = "nrldpc_decode_z64_pair.h"
 # = NRLDPC_Z64_LIST (nrldpc_kernels.h): the sizes where the compile-time-Z kernel beats the run-time-Z one
 Z64_BG1 = (60, 64, 104, 112, 120, 128, 144, 176, 192, 208, 224, 240, 256, 288, 320, 352, 384)
 Z64_BG2 = (52, 60, 64, 88, 96, 104, 112, 120, 128, 144, 192, 208, 224, 240, 256, 288, 320, 352, 384)
@@ -55,7 +62,10 @@ Z64I = [
 ]
 # = NRLDPC_Z64_NL_LIST: (BG, Z, active layers) with pipelined kernels of their own
 Z64_NL = [(1, 384, 5), (1, 384, 13), (1, 384, 24), (2, 384, 32), (2, 384, 22), (2, 384, 17), (2, 384, 12), (2, 384, 9), (2, 384, 7), (2, 208, 21)]
-HEADERS = ["nrldpc_kernels.h", "nrldpc_dispatch_lists.h", "nrldpc_sched.h", "nrldpc_device.h", "nrldpc_decode_z64.h", "nrldpc_decode_z64s.h", "nrldpc_decode_z64p.h", "nrldpc_wave.h", "nrldpc_host_quant.h", "nrldpc_hostpath.h", "nrldpc_bp.h", "nrldpc_cwout.h", "nrldpc_modem.h", "nrldpc_ratematch_ex.h"]
+# (BG, Z) whose units -- the Z64_NL units of the same pair included: they share the code -- compile from Z64Q_SOURCE.  A size joins only with
+# a timed A/B of its own against the NRLDPC_BUILD_NOPAIR library (profiles/r07_pair_search_ab.txt)
+Z64_PAIR = [(1, 384)]
+HEADERS = [Z64Q_HEADER, "nrldpc_kernels.h", "nrldpc_dispatch_lists.h", "nrldpc_sched.h", "nrldpc_device.h", "nrldpc_decode_z64.h", "nrldpc_decode_z64s.h", "nrldpc_decode_z64p.h", "nrldpc_wave.h", "nrldpc_host_quant.h", "nrldpc_hostpath.h", "nrldpc_bp.h", "nrldpc_cwout.h", "nrldpc_modem.h", "nrldpc_ratematch_ex.h"]
 # -mllvm -enable-post-misched=false: LLVM's post-register-allocation machine scheduler off.  The decoder loops are VALU-issue bound and
 # hand-ordered (pinned read batches, s_setprio windows, launder() fences); the pre-RA scheduler keeps that order, the post-RA pass
 # reshuffles it for latencies the other waves of the CU already hide.  Measured on the MI355X over every lifting size, whole library
@@ -74,7 +84,7 @@ def _hipcc():
 
 
 def _deps():
-    d = [os.path.join(CSRC, f) for f in SOURCES + HEADERS + [Z64_SOURCE, Z64P_SOURCE]]
+    d = [os.path.join(CSRC, f) for f in SOURCES + HEADERS + [Z64_SOURCE, Z64P_SOURCE, Z64Q_SOURCE]]
     d += [os.path.join(INCLUDE, "nrldpc.h"), os.path.join(INCLUDE, "nr_bg_tables.h"), os.path.abspath(__file__)]
     return [p for p in d if os.path.exists(p)]
 
@@ -107,6 +117,23 @@ def kernel_id():
             h.update(f.read())
     h.update(" ".join(FLAGS).encode())
     return h.hexdigest()[:16]
+
+
+def pair_search_id():
+    """Hash of the two files that hold the paired two-smallest search.  They are outside kernel_id() (the sources it hashes are unchanged
+    by them), yet the headline kernel is compiled from them: the profile summaries under profiles/ carry this id next to the kernel id
+    (tests/test_pair_search_api.py), so an edit of either file without a profile refresh is caught."""
+    h = hashlib.sha256()
+    for f in (Z64Q_HEADER, Z64Q_SOURCE):
+        h.update(f.encode() + b"\0")
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()[:16]
+
+
+def z64_source(bg, z):
+    """The instantiation file the block-geometry unit(s) of (bg, z) compile from."""
+    return Z64Q_SOURCE if (bg, z) in Z64_PAIR and not NOPAIR else Z64_SOURCE
 
 
 _INC = None
@@ -164,7 +191,7 @@ def build_lib(force=False, verbose=False, jobs=None):
               ['-DNRLDPC_BUILD_ID="%s"' % sid, '-DNRLDPC_KERNEL_ID="%s"' % kernel_id()] if f == "nrldpc_capi.hip" else
              ["-DNRLDPC_Z64I_FORCE_MODE=7"] if (ALLMODES and f == "nrldpc_decode.hip") else [])
              for f in SOURCES]
-    units += [(os.path.join(CSRC, Z64_SOURCE), os.path.join(OBJDIR, "z64_%d_%d.o" % (bg, z)),
+    units += [(os.path.join(CSRC, z64_source(bg, z)), os.path.join(OBJDIR, "z64_%d_%d.o" % (bg, z)),
                ["-DNRLDPC_Z64_BG=%d" % bg, "-DNRLDPC_Z64_Z=%d" % z]) for bg, z in Z64_PAIRS]
     units += [(os.path.join(CSRC, Z64P_SOURCE), os.path.join(OBJDIR, "z64p_%d_%d.o" % (bg, z)),
                ["-DNRLDPC_Z64_BG=%d" % bg, "-DNRLDPC_Z64_Z=%d" % z]) for bg, z in Z64P_PAIRS]
@@ -175,10 +202,10 @@ def build_lib(force=False, verbose=False, jobs=None):
     units += [(os.path.join(CSRC, Z64P_SOURCE), os.path.join(OBJDIR, "z64i_%d_%d.o" % (bg, z)),
                ["-DNRLDPC_Z64_BG=%d" % bg, "-DNRLDPC_Z64_Z=%d" % (z * ncw), "-DNRLDPC_Z64_ILV=%d" % ncw, "-DNRLDPC_Z64I_ZR=%d" % z,
                 "-DNRLDPC_Z64S_DUAL=0", "-DNRLDPC_Z64I_MODE=%d" % (7 if ALLMODES else mode)]) for bg, z, ncw, mode in Z64I]
-    units += [(os.path.join(CSRC, Z64_SOURCE), os.path.join(OBJDIR, "z64_%d_%d_nl%d.o" % (bg, z, nl)),
+    units += [(os.path.join(CSRC, z64_source(bg, z)), os.path.join(OBJDIR, "z64_%d_%d_nl%d.o" % (bg, z, nl)),
                ["-DNRLDPC_Z64_BG=%d" % bg, "-DNRLDPC_Z64_Z=%d" % z, "-DNRLDPC_Z64_NL=%d" % nl]) for bg, z, nl in Z64_NL]
     # every decoder unit gets a name space of its own for the -D-dependent templates (NRLDPC_UNIT, nrldpc_decode_z64.h)
-    units = [(src, obj, defs + (["-DNRLDPC_UNIT=u_" + os.path.splitext(os.path.basename(obj))[0]] if os.path.basename(src) in (Z64_SOURCE, Z64P_SOURCE) else []))
+    units = [(src, obj, defs + (["-DNRLDPC_UNIT=u_" + os.path.splitext(os.path.basename(obj))[0]] if os.path.basename(src) in (Z64_SOURCE, Z64P_SOURCE, Z64Q_SOURCE) else []))
              for src, obj, defs in units]
     # An object is reused only when it was compiled from exactly these inputs: contents of its source and of every header
     # it includes (transitively, by scanning #include "..." lines: a change to the C ABI does not recompile 130 decoder

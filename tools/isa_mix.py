@@ -74,10 +74,12 @@ def main():
         co = os.path.join(td, "k.co")
         import importlib
         sys.path.insert(0, ROOT)
-        flags = [f for f in importlib.import_module("ldpc-3gpp-matlab_amd.build").FLAGS if f != "-fPIC"]  # the library's own flags (scheduling options included)
+        bld = importlib.import_module("ldpc-3gpp-matlab_amd.build")
+        flags = [f for f in bld.FLAGS if f != "-fPIC"]  # the library's own flags (scheduling options included)
+        inst = bld.z64_source(a.bg, a.z)  # the file the library's unit of this size compiles from (NRLDPC_BUILD_NOPAIR=1: the plain one)
         subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, "-I" + os.path.join(ROOT, "include"),
                                "-I" + CSRC, "-DNRLDPC_Z64_BG=%d" % a.bg, "-DNRLDPC_Z64_Z=%d" % a.z, "--cuda-device-only",
-                               "--no-gpu-bundle-output", "-c", os.path.join(CSRC, "nrldpc_decode_z64_inst.hip"), "-o", co])
+                               "--no-gpu-bundle-output", "-c", os.path.join(CSRC, inst), "-o", co])
         dis = subprocess.check_output([OBJDUMP, "-d", co], text=True)
     # the fixed-iteration build: row form <BG, Z, NCWG, FULL=1, PLAIN=1, ETP=0, NL>; split form <BG, Z, ETP=0, NL>
     # (... with every row active: NL = 46 / 42 -- the unit also holds the builds with a run-time layer count, NL = 0)
@@ -125,8 +127,8 @@ def main():
         c = "VALU" if op.startswith("v_") else "LDS" if op.startswith("ds_") else "barrier" if op == "s_barrier" else \
             "waitcnt/nop" if op in ("s_waitcnt", "s_nop") else "SALU/branch" if op.startswith("s_") else "VMEM"
         cls[c] += n
-    print("# tools/isa_mix.py: iteration loop%s of the %s kernel, BG=%d Z=%d, fixed iteration count (device-only compile of the tree's sources)" % (
-        "s (one per half, summed)" if a.form == "split" else "", "two-threads-per-row (split)" if a.form == "split" else "one-thread-per-row", a.bg, a.z))
+    print("# tools/isa_mix.py: iteration loop%s of the %s kernel, BG=%d Z=%d, fixed iteration count (device-only compile of %s)" % (
+        "s (one per half, summed)" if a.form == "split" else "", "two-threads-per-row (split)" if a.form == "split" else "one-thread-per-row", a.bg, a.z, inst))
     print("# loop = code between a long backward branch and its target: %d instructions, %.1f KB in total" % (len(loop), loop_bytes / 1024.0))
     print("instruction classes per iteration, summed over the waves that serve one block of 64 rows:", dict(cls))
     edges = {1: 316, 2: 197}[a.bg]
@@ -165,8 +167,8 @@ def main():
     if a.json:
         import importlib, json
         sys.path.insert(0, ROOT)
-        kid = importlib.import_module("ldpc-3gpp-matlab_amd.build").kernel_id()
-        json.dump({"nrldpc_kernel_id": kid, "bg": a.bg, "Z": a.z, "form": a.form, "valu_instructions_per_iteration_all_waves_of_a_row": cls["VALU"],
+        kid = bld.kernel_id()
+        json.dump({"nrldpc_kernel_id": kid, "_pair_search_id": bld.pair_search_id(), "instantiation_file": inst, "bg": a.bg, "Z": a.z, "form": a.form, "valu_instructions_per_iteration_all_waves_of_a_row": cls["VALU"],
                    "valu_ns_per_iteration_all_waves_of_a_row": total, "lds_instructions": cls["LDS"], "barriers": cls["barrier"],
                    "loop_bytes": loop_bytes, "source": "tools/isa_mix.py (static disassembly x measured issue intervals)"},
                   open(a.json, "w"), indent=1)

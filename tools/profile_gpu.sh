@@ -14,7 +14,10 @@ python - > $OUT/ids.json <<PY
 import importlib, json, sys
 sys.path.insert(0, "$ROOT")
 L = importlib.import_module("ldpc-3gpp-matlab_amd").load()
-print(json.dumps({"nrldpc_build_id": L.nrldpc_build_id().decode(), "nrldpc_kernel_id": L.nrldpc_kernel_id().decode()}))
+B = importlib.import_module("ldpc-3gpp-matlab_amd.build")
+assert L.nrldpc_build_id().decode() == B.source_id(), "the loaded library was not built from this tree"
+print(json.dumps({"nrldpc_build_id": L.nrldpc_build_id().decode(), "nrldpc_kernel_id": L.nrldpc_kernel_id().decode(),
+                  "pair_search_id": B.pair_search_id()}))
 PY
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- $BENCH > $OUT/stats.log 2>&1
 pmc() { # name, counters...

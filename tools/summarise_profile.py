@@ -8,6 +8,8 @@ Writes
   profiles/<tag>_bench_pmc_summary.json    mean per launch of every PMC counter, dominant kernel only
   profiles/<tag>_traffic_bytes_per_launch.json   HBM bytes per launch (bench.py reads this for roofline.traffic)
 Every summary carries nrldpc_build_id / nrldpc_kernel_id of the library that was profiled (gpurun_out/prof_<tag>/ids.json).
+It also carries, as "_pair_search_id", build.pair_search_id() of the tree that library was built from: the headline unit compiles
+from two files that the kernel id does not cover (nrldpc_decode_z64q_inst.hip, nrldpc_decode_z64_pair.h; tests/test_pair_search_api.py).
 The kernel-trace average excludes the first (warm-up) launch of the dominant kernel.
 
 HBM correction (MI355X_MICROARCH.md, HBM / rocprofv3 section): FETCH_SIZE and WRITE_SIZE are in KiB; on
@@ -63,6 +65,7 @@ def main():
         pass
     summary["_nrldpc_build_id"] = ids.get("nrldpc_build_id")
     summary["_nrldpc_kernel_id"] = ids.get("nrldpc_kernel_id")
+    summary["_pair_search_id"] = ids.get("pair_search_id")
     # per-launch durations of the dominant kernel from the kernel trace, first (warm-up) launch excluded
     trace = os.path.join(src, "stats", "stats_kernel_trace.csv")
     if os.path.exists(trace):
@@ -93,6 +96,7 @@ def main():
             "hbm_bytes_per_codeword": hbm / batch,
         }
         out["nrldpc_build_id"], out["nrldpc_kernel_id"] = ids.get("nrldpc_build_id"), ids.get("nrldpc_kernel_id")
+        out["_pair_search_id"] = ids.get("pair_search_id")
         with open(os.path.join(dst, tag + "_traffic_bytes_per_launch.json"), "w") as f:
             json.dump(out, f, indent=1)
         print("HBM bytes per launch:", hbm, "per codeword:", hbm / batch)
