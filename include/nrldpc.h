@@ -427,6 +427,31 @@ int nrldpc_demodulate_dev(const float* d_rx /* [n_sym][2] */, int64_t n_sym, int
                           void* d_out /* [n_sym*Q_m]: out_dtype for the two LLR methods, uint8 {0,1} for HARD */,
                           int32_t out_dtype /* NRLDPC_LLR_F32 / _F16; not read for HARD */, void* stream);
 
+/* The middle of the channel leg on its own: step(hChan, tx) of plot_BLER_vs_SNR.m:131, the mirror of comm.AWGNChannel.
+ * rx[s] = tx[s] + w[s] for n_sym symbols as interleaved float (re, im) pairs (complex64).  Stateless, current HIP device,
+ * asynchronous on `stream`.  Added without a revision bump (a binding finds it by symbol); nothing an earlier caller uses changed.
+ *
+ * Noise: w is exactly the noise nrldpc_awgn_llr_dev draws for the same (seed, first_symbol).  The global index of local symbol s is
+ * first_symbol + s; the aligned pair (2c, 2c+1) of the global index shares one Philox-4x32-10 block, key = seed, counter
+ * (c, c >> 32, 0, 0); words 0,1 feed the even symbol, words 2,3 the odd one; a word becomes the 24-bit uniform
+ * ((w >> 8) + 0.5) / 2^24; Box-Muller on the two uniforms of a symbol (the hardware's log2 / sqrt / sin / cos) gives its two rails,
+ * each scaled by sigma = sqrt(N0 / 2).  Each noise component is rounded to f32 and added to the symbol with one f32 add.
+ * N0 is the complex noise variance: `variance` for every symbol, or, when d_variance is not null, d_variance[s] for symbol s (device,
+ * n_sym floats; replaces the scalar) -- what nrldpc_demodulate_dev accepts.  sigma is formed from the f32 N0 on the device in both
+ * cases: an array filled with one value gives the scalar call's bits.  variance == 0 gives rx == tx as numbers.
+ * A call over a buffer equals calls over its parts bit for bit at any split, given each part's own first_symbol.  Any float-aligned
+ * address and any n_sym >= 0 are served.  d_rx == d_tx (in place) is allowed; any other overlap is unspecified.
+ * nrldpc_demodulate_dev(NRLDPC_DEMOD_LLR, variance = N0) of nrldpc_awgn_dev(nrldpc_modulate_dev(g), N0, seed, first_symbol) agrees with
+ * nrldpc_awgn_llr_dev(g, EsN0_dB, seed, first_symbol) for N0 = 10^(-EsN0_dB/10) within |dLLR| <= 1e-3 * max(1, |LLR|)
+ * (tests/test_awgn_gpu.py; measured maximum: DESIGN.md section 4.14).
+ * Errors, all before any device call, NRLDPC_ERR_ARG: a negative n_sym; a null d_tx or d_rx with n_sym > 0; d_variance == NULL and
+ * `variance` negative or not finite; first_symbol + n_sym overflowing 64 bits.  n_sym == 0 returns NRLDPC_OK without a launch.
+ * Non-positive or non-finite array entries, and non-finite symbols: unspecified. */
+int nrldpc_awgn_dev(const float* d_tx /* [n_sym][2] */, int64_t n_sym,
+                    float variance, const float* d_variance /* [n_sym], nullable */,
+                    uint64_t seed, uint64_t first_symbol,
+                    float* d_rx /* [n_sym][2]; may equal d_tx */, void* stream);
+
 /* Kernel timing: when enabled, every *_dev / host call records HIP events around its kernel on the
  * launch stream; nrldpc_last_kernel_ms synchronises on the stop event and returns the duration. */
 int nrldpc_set_timing(nrldpc_handle h, int32_t enabled);

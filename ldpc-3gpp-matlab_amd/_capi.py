@@ -106,7 +106,7 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_set_layers", "nrldpc_set_llr_dtype", "nrldpc_last_layers", "nrldpc_count_layers", "nrldpc_pool_set_layers", "nrldpc_pool_decode_packed",
            "nrldpc_decode_packed_layers", "nrldpc_pool_set_timing", "nrldpc_pool_last_kernel_ms", "nrldpc_last_host_phases", "nrldpc_payload_bits_dev",
            "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm", "nrldpc_decode_cw", "nrldpc_decode_cw_dev",
-           "nrldpc_modulate_dev", "nrldpc_demodulate_dev", "nrldpc_rate_recover_ex_dev"]
+           "nrldpc_modulate_dev", "nrldpc_demodulate_dev", "nrldpc_rate_recover_ex_dev", "nrldpc_awgn_dev"]
 
 _lib = None
 
@@ -180,6 +180,8 @@ def load():
     L.nrldpc_awgn_llr_dev.argtypes = [vp, C.c_int64, i32, C.c_float, C.c_uint64, C.c_uint64, vp, vp]
     L.nrldpc_modulate_dev.argtypes = [vp, C.c_int64, i32, vp, vp]
     L.nrldpc_demodulate_dev.argtypes = [vp, C.c_int64, i32, i32, C.c_float, vp, vp, i32, vp]
+    if hasattr(L, "nrldpc_awgn_dev"):  # added without a revision bump: a library selected with NRLDPC_LIB may lack it
+        L.nrldpc_awgn_dev.argtypes = [vp, C.c_int64, C.c_float, vp, C.c_uint64, C.c_uint64, vp, vp]
     L.nrldpc_crc_attach_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_rate_match_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_pool_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), i32, i32, C.POINTER(vp)]
@@ -599,6 +601,20 @@ def demodulate_dev(d_rx, n_sym, Q_m, d_out, method="llr", variance=1.0, d_varian
     d_variance: a device array of n_sym floats, one per symbol, that replaces it."""
     check(load().nrldpc_demodulate_dev(_ptr(d_rx), int(n_sym), int(Q_m), demod_method_code(method), float(variance),
                                        _ptr(d_variance), _ptr(d_out), int(out_dtype), C.c_void_p(stream)))
+
+
+def awgn_dev(d_tx, n_sym, d_rx, variance=1.0, d_variance=None, seed=0, first_symbol=0, stream=None):
+    """nrldpc_awgn_dev: n_sym complex64 symbols at d_tx + complex Gaussian noise -> d_rx (which may be d_tx): the noise
+    nrldpc_awgn_llr_dev draws for the same (seed, first_symbol), first_symbol being the global index of the first symbol.
+    variance: the complex noise variance N0; d_variance: a device array of n_sym floats, one per symbol, that replaces it."""
+    L = load()
+    if not hasattr(L, "nrldpc_awgn_dev"):
+        raise NRLDPCError("%s has no nrldpc_awgn_dev: the stand-alone AWGN stage needs a library built from this tree "
+                          "(NRLDPC_LIB selects an older one?)" % lib_path())
+    if not 0 <= int(first_symbol) < 1 << 64:
+        raise NRLDPCError("first_symbol should lie in [0, 2^64)")
+    check(L.nrldpc_awgn_dev(_ptr(d_tx), int(n_sym), float(variance), _ptr(d_variance), int(seed) % (1 << 64), int(first_symbol),
+                            _ptr(d_rx), C.c_void_p(stream or 0)))
 
 
 def payload_bits_dev(seed, first_block, n_tb, A, d_a, stream=0):

@@ -2072,6 +2072,22 @@ int nrldpc_demodulate_dev(const float* d_rx, int64_t n_sym, int32_t Q_m, int32_t
     return NRLDPC_OK;
 }
 
+// ---- stand-alone AWGN stage (nrldpc_awgn.hip): every check before any device call ----
+int nrldpc_awgn_dev(const float* d_tx, int64_t n_sym, float variance, const float* d_variance, uint64_t seed, uint64_t first_symbol,
+                    float* d_rx, void* stream) {
+    if (n_sym < 0) return fail(NRLDPC_ERR_ARG, "negative symbol count");
+    if (n_sym > 0 && (!d_tx || !d_rx)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (!d_variance && !(variance >= 0.0f && std::isfinite(variance))) return fail(NRLDPC_ERR_ARG, "variance must be non-negative and finite");
+    if (first_symbol + (uint64_t)n_sym < first_symbol) return fail(NRLDPC_ERR_ARG, "first_symbol + n_sym overflows 64 bits");
+    if (n_sym == 0) return NRLDPC_OK;
+    nrldpc::AwgnArgs a;
+    a.tx = d_tx; a.var = d_variance; a.rx = d_rx; a.n_sym = n_sym; a.seed = seed; a.first_symbol = first_symbol;
+    a.variance = variance; // (not read when the array is given)
+    hipError_t e = nrldpc::launch_awgn(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "AWGN kernel launch");
+    return NRLDPC_OK;
+}
+
 } // extern "C"
 namespace nrldpc { // nrldpc_channel.hip (declared here, not in nrldpc_kernels.h: that header is part of the decoder kernels' identity, nrldpc_kernel_id)
 hipError_t launch_payload_bits(uint64_t seed, uint64_t first_block, int32_t n_tb, int32_t A, uint8_t* out, hipStream_t stream);

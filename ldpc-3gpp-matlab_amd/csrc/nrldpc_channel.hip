@@ -14,35 +14,20 @@
 
 #include "nrldpc_kernels.h"
 #include "nrldpc_modem.h"
+#include "nrldpc_noise.h"
 
 namespace nrldpc {
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
+// philox4x32_10 / box_muller, the noise draw: nrldpc_noise.h (shared with the stand-alone AWGN stage, nrldpc_awgn.hip)
 // pam_level<NB> / rail_llr<NB>, the rail arithmetic: nrldpc_modem.h (shared with the stand-alone demapper)
 
 // LLRs of one symbol from its bits and the two uniform words of its noise sample
 template <int QM> __device__ __forceinline__ void symbol_llr(const ChanArgs& a, const uint8_t* g, uint32_t w1, uint32_t w2, float* o) {
-    // Box-Muller on 24-bit uniforms in (0,1): exact in f32
-    const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f), u2 = ((float)(w2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    // The hardware's own transcendentals: v_sin_f32 / v_cos_f32 take their argument in REVOLUTIONS, so sin(2 pi u2) is one
-    // instruction on u2 itself -- no range reduction (the library sincosf carries a Payne-Hanek path for arguments it never gets
-    // here); v_log_f32 is log2, v_sqrt_f32 is within 1 ulp.  The kernel issues VALU instructions, not bytes (438 per thread before,
-    // most of them here and in Philox): it is bound by that, not by HBM.  Results move by ~1e-6 relative; the test's tolerance on an
-    // LLR is 5e-4 (tests/test_chain_gpu.py).
-    const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1)) * a.sigma; // -2 ln u1 = -2 ln2 log2 u1; sigma = sqrt(N0/2) per rail
-    const float sn = __builtin_amdgcn_sinf(u2), cs = __builtin_amdgcn_cosf(u2);
+    // Box-Muller on the hardware's transcendentals (nrldpc_noise.h).  The kernel issues VALU instructions, not bytes (438 per thread
+    // before, most of them there and in Philox): it is bound by that, not by HBM.  Results move by ~1e-6 relative; the test's tolerance
+    // on an LLR is 5e-4 (tests/test_chain_gpu.py).
+    float rad, cs, sn;
+    box_muller(w1, w2, a.sigma, rad, cs, sn); // sigma = sqrt(N0/2) per rail
     const float ni = rad * cs, nq = rad * sn;
     if constexpr (QM == 1) { // comm.PSKModulator order 2, phase offset pi/4 (NRModulator.m:73): LLR = 4 Re(rx e^{-j pi/4}) / N0
         const float tx = (g[0] & 1u) ? -1.0f : 1.0f;

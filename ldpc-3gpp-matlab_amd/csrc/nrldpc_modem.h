@@ -1,5 +1,6 @@
 // nrldpc_modem.h -- what the fused channel kernel (nrldpc_channel.hip) and the stand-alone symbol mapper / soft demapper
-// (nrldpc_modem.hip) share: the TS 38.211 rail arithmetic, and the launch arguments of the stand-alone kernels.
+// (nrldpc_modem.hip) share: the TS 38.211 rail arithmetic, and the launch arguments of the stand-alone kernels, the stand-alone AWGN
+// stage (nrldpc_awgn.hip) among them.
 // (Not in nrldpc_kernels.h: that header is part of the decoder kernels' identity, nrldpc_kernel_id.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +51,14 @@ template <int NB> __device__ __forceinline__ void rail_llr(float y, float inv_n0
         llr[k] = (mx[k][0] - mx[k][1]) + 0.6931471805599453f * (__builtin_amdgcn_logf(sm[k][0]) - __builtin_amdgcn_logf(sm[k][1]));
 }
 
+// N dwords at an address that is dword-aligned and no more: the compiler picks dwordx4 / x3 / x2 pieces
+template <int N> __device__ __forceinline__ void load_words(const void* p, uint32_t (&w)[N]) {
+    __builtin_memcpy(w, __builtin_assume_aligned(p, 4), 4 * N);
+}
+template <int N> __device__ __forceinline__ void store_words(void* p, const uint32_t (&w)[N]) {
+    __builtin_memcpy(__builtin_assume_aligned(p, 4), w, 4 * N);
+}
+
 // ---- stand-alone mapper / demapper (nrldpc_modem.hip) ----------------------------------------------------------------------------
 struct ModArgs {
     const uint8_t* g; // [n_sym * Qm] bits, one byte each
@@ -68,5 +77,16 @@ struct DemodArgs {
 };
 hipError_t launch_modulate(const ModArgs& a, hipStream_t stream);
 hipError_t launch_demodulate(const DemodArgs& a, hipStream_t stream);
+
+// ---- stand-alone AWGN stage (nrldpc_awgn.hip) ------------------------------------------------------------------------------------
+struct AwgnArgs {
+    const float* tx;  // [n_sym][2] (re, im)
+    const float* var; // [n_sym] complex noise variance per symbol, or null: `variance` for every symbol
+    float* rx;        // [n_sym][2]; may equal tx
+    int64_t n_sym;
+    uint64_t seed, first_symbol; // Philox key; global index of local symbol 0
+    float variance;
+};
+hipError_t launch_awgn(const AwgnArgs& a, hipStream_t stream);
 
 } // namespace nrldpc

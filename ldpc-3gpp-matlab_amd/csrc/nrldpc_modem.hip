@@ -27,13 +27,7 @@
 
 namespace nrldpc {
 
-// N dwords at an address that is dword-aligned and no more: the compiler picks dwordx4 / x3 / x2 pieces
-template <int N> __device__ __forceinline__ void load_words(const void* p, uint32_t (&w)[N]) {
-    __builtin_memcpy(w, __builtin_assume_aligned(p, 4), 4 * N);
-}
-template <int N> __device__ __forceinline__ void store_words(void* p, const uint32_t (&w)[N]) {
-    __builtin_memcpy(__builtin_assume_aligned(p, 4), w, 4 * N);
-}
+// load_words<N> / store_words<N>, the wide accesses at a dword-aligned address: nrldpc_modem.h (shared with nrldpc_awgn.hip)
 
 constexpr int MODEM_BLOCK = 256, MODEM_MAX_GRID = 1 << 20;
 template <int QM> struct SymbolsPerThread { static constexpr int value = QM == 1 ? 4 : 2; };

@@ -149,6 +149,21 @@ def payload_bits(seed, first_block, n, A, dev):
 ATTEMPT_STRIDE = 1 << 40  # Philox symbol counter = attempt * 2^40 + global block index * symbols per block + symbol
 
 
+def awgn_channel(seed):
+    """The library's own noise as a channel of simulate_point_device: a callable (tx, N0, first_symbol) that adds to tx, in place,
+    the noise the fused kernel draws for (seed, first_symbol) (nrldpc_awgn_dev) and returns tx."""
+    def channel(tx, N0, first_symbol):
+        import torch
+        from ._capi import NRLDPCError, awgn_dev
+        if not (torch.is_tensor(tx) and tx.is_cuda and tx.dtype == torch.complex64 and tx.is_contiguous()):
+            raise NRLDPCError("awgn_channel works in place: tx should be a contiguous complex64 device tensor")
+        with torch.cuda.device(tx.device):
+            awgn_dev(tx.data_ptr(), tx.numel(), tx.data_ptr(), variance=N0, seed=seed, first_symbol=first_symbol,
+                     stream=torch.cuda.current_stream(tx.device).cuda_stream)
+        return tx
+    return channel
+
+
 def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_block, channel=None, llr_dtype=None):
     """simulate_point with every stage on the GPU(s) (rows N1-N4 of SURVEY.md section 8f): payload, CRC attachment,
     encoding, rate matching, modulation + AWGN + exact LLRs (one HIP kernel, nrldpc_awgn_llr_dev), rate recovery, decoding,
@@ -166,7 +181,9 @@ def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_
     tx is the step's complex64 device tensor [n][G / Q_m] of unit-power symbols, N0 the noise variance of the SNR point,
     first_symbol the global index of tx's first symbol (what the fused kernel counts its noise by); it returns the received
     symbols, same shape and type, on the same device and stream.  :130-132 then run as three steps, nrldpc_modulate_dev ->
-    channel -> nrldpc_demodulate_dev (exact LLRs, Variance = N0); nothing else in the loop changes.
+    channel -> nrldpc_demodulate_dev (exact LLRs, Variance = N0); nothing else in the loop changes.  channel = "awgn" is
+    awgn_channel(seed), the library's stand-alone noise stage: the fused kernel's draw, a function of the global symbol index, so the
+    outcome vector keeps the shard-count invariance of the fused path.
 
     llr_dtype: None / np.float32, or np.float16 -- with a channel of the caller's the demapper then writes f16 LLRs and the decode
     chain is stepped with them as they are (no f32 copy of g_tilde exists).  The fused kernel writes f32 only: not read without
@@ -176,6 +193,10 @@ def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_
     llr_dt = np.dtype(np.float32 if llr_dtype is None else llr_dtype)
     if llr_dt not in (np.dtype(np.float32), np.dtype(np.float16)):
         raise UnsupportedParameters("llr_dtype should be numpy float32 or float16, not %r." % (llr_dtype,))
+    if isinstance(channel, str):
+        if channel != "awgn":
+            raise UnsupportedParameters('channel should be None, "awgn" or a callable, not %r.' % (channel,))
+        channel = awgn_channel(seed)
     half = channel is not None and llr_dt == np.float16
     D = len(chains)
     cuts = [shard_range(batch, d, D)[0] for d in range(D)] + [batch]   # contiguous slices (shard.py), as every multi-GPU path here
@@ -283,7 +304,8 @@ def plot_BLER_vs_SNR(A=3842, R=1 / 3, BG=2, Modulation="QPSK", rv_id_sequence=(0
                      target_block_errors=3, target_BLER=1e-3, EsN0_start=0.0, EsN0_delta=0.5, seed=0,
                      results_dir="results", batch=256, max_points=200, decoder_kwargs=None, device=False, devices=None, channel=None):
     """Same positional parameters and defaults as plot_BLER_vs_SNR.m:1,30-42 (no figure is drawn).
-    channel: with device=True, the caller's channel in place of the fused kernel's AWGN (simulate_point_device).
+    channel: with device=True, the caller's channel, or "awgn" for the library's stand-alone noise stage, in place of the fused kernel
+    (simulate_point_device).
     device=True keeps every stage on the GPU (simulate_point_device); devices = HIP ordinals of the shards (default [0];
     an ordinal may repeat: logical shards on one GPU) -- the result file does not depend on their number.
     Returns {(A, R, BG): [(EsN0, BLER, blocks), ...]}."""

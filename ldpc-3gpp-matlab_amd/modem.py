@@ -1,6 +1,7 @@
-"""NRModulator / NRDemodulator: mirrors of the reference's two modulation System objects (NRModulator.m, NRDemodulator.m).
+"""NRModulator / NRDemodulator: mirrors of the reference's two modulation System objects (NRModulator.m, NRDemodulator.m), and
+AWGNChannel, the mirror of the comm.AWGNChannel between them (plot_BLER_vs_SNR.m:50,105,131).
 
-step() runs the library's mapper / demapper kernels (nrldpc_modulate_dev / nrldpc_demodulate_dev) and nothing else: a torch device
+step() runs the library's mapper / demapper / noise kernels (nrldpc_modulate_dev / nrldpc_demodulate_dev / nrldpc_awgn_dev) and nothing else: a torch device
 tensor is used where it lies, on its device's current stream; a numpy array is staged through device 0 and comes back as a numpy
 array.  Bits are bytes {0,1} along the last axis, symbols complex64 of unit average power, LLRs positive for bit 0.
 """
@@ -120,3 +121,100 @@ class NRDemodulator(_Modem):
 
     def _method_name(self):
         return ("llr", "approx", "hard")[self._method]
+
+
+NOISE_METHODS = ("Signal to noise ratio (Eb/No)", "Signal to noise ratio (Es/No)", "Signal to noise ratio (SNR)", "Variance")
+VARIANCE_SOURCES = ("Property", "Input port")
+
+
+class AWGNChannel:
+    """hChan = comm.AWGNChannel('NoiseMethod', 'Signal to noise ratio (SNR)'); hChan.SNR = EsN0; rx = step(hChan, tx)
+    (plot_BLER_vs_SNR.m:50,105,131).  Properties, defaults and the variance they give are comm.AWGNChannel's; every one of them is
+    tunable between steps.  N0 (read-only, no device needed) is the complex noise variance in use, derived in float64:
+        Eb/No:    EsNo = EbNo + 10 log10(BitsPerSymbol), then as Es/No
+        Es/No:    SignalPower * SamplesPerSymbol / 10^(EsNo/10)
+        SNR:      SignalPower / 10^(SNR/10)
+        Variance: Variance (VarianceSource "Property"), or step(tx, var) (VarianceSource "Input port": a scalar, or one value per
+                  symbol as an array shaped like tx)
+    The noise is the library's counter-based draw (nrldpc_awgn_dev: the fused kernel's noise for the same seed and symbol index), keyed
+    by Seed.  The object counts the symbols it has stepped -- the stream position of RandomStream = 'mt19937ar with seed': two steps
+    draw what one step over the concatenation draws, and reset() rewinds.  step(tx, first_symbol=k) draws at global symbol index k and
+    leaves the counter alone (a sharded caller).  Any shape; the symbol order is the flattened C order."""
+
+    def __init__(self, NoiseMethod=NOISE_METHODS[0], EbNo=10.0, EsNo=10.0, SNR=10.0, BitsPerSymbol=1, SignalPower=1.0,
+                 SamplesPerSymbol=1, VarianceSource="Property", Variance=1.0, Seed=0):
+        self.NoiseMethod = NoiseMethod
+        self.VarianceSource = VarianceSource
+        self.EbNo, self.EsNo, self.SNR, self.BitsPerSymbol = EbNo, EsNo, SNR, BitsPerSymbol
+        self.SignalPower, self.SamplesPerSymbol, self.Variance, self.Seed = SignalPower, SamplesPerSymbol, Variance, Seed
+        self._count = 0
+
+    @property
+    def NoiseMethod(self):
+        return self._noise_method
+
+    @NoiseMethod.setter
+    def NoiseMethod(self, m):
+        if m not in NOISE_METHODS:
+            raise UnsupportedParameters("unknown NoiseMethod %r (one of %s)" % (m, ", ".join(NOISE_METHODS)))
+        self._noise_method = m
+
+    @property
+    def VarianceSource(self):
+        return self._variance_source
+
+    @VarianceSource.setter
+    def VarianceSource(self, v):
+        if v not in VARIANCE_SOURCES:
+            raise UnsupportedParameters("unknown VarianceSource %r (one of %s)" % (v, ", ".join(VARIANCE_SOURCES)))
+        self._variance_source = v
+
+    @property
+    def N0(self):
+        """The complex noise variance the next step(tx) uses (float64)."""
+        i = NOISE_METHODS.index(self._noise_method)
+        if i == 3:
+            return float(self.Variance)
+        if i == 2:
+            return float(self.SignalPower) / 10.0 ** (float(self.SNR) / 10.0)
+        EsNo = float(self.EsNo) if i == 1 else float(self.EbNo) + 10.0 * np.log10(float(self.BitsPerSymbol))
+        return float(self.SignalPower) * float(self.SamplesPerSymbol) / 10.0 ** (EsNo / 10.0)
+
+    def __call__(self, *a, **kw):
+        return self.step(*a, **kw)
+
+    def reset(self):
+        """Rewind the noise stream: the same steps then draw the same noise."""
+        self._count = 0
+
+    def release(self):
+        pass
+
+    def step(self, tx, var=None, first_symbol=None):
+        """tx [...] complex symbols -> tx + noise, same shape (a new array; tx is left as it is)."""
+        import torch
+        port = self._noise_method == "Variance" and self._variance_source == "Input port"
+        if port != (var is not None):
+            raise _capi.NRLDPCError("step(tx, var) goes with NoiseMethod 'Variance' and VarianceSource 'Input port', step(tx) with "
+                                    "everything else")
+        y, host = _Modem._to_device(tx, torch.complex64)
+        n0, d_var = self.N0, None
+        if port:
+            if (var.ndim if _is_tensor(var) else np.ndim(var)) != 0:
+                if _is_tensor(var):
+                    d_var = var.to(device=y.device, dtype=torch.float32).contiguous()
+                else:
+                    d_var = torch.from_numpy(np.ascontiguousarray(var, np.float32)).to(y.device)
+                if d_var.numel() != y.numel():
+                    raise _capi.NRLDPCError("a variance array should hold one value per symbol")
+                n0 = 1.0
+            else:
+                n0 = float(var)
+        rx = torch.empty_like(y)
+        with torch.cuda.device(y.device):
+            _capi.awgn_dev(y.data_ptr(), y.numel(), rx.data_ptr(), variance=n0, d_variance=d_var.data_ptr() if d_var is not None else None,
+                           seed=self.Seed, first_symbol=self._count if first_symbol is None else first_symbol,
+                           stream=torch.cuda.current_stream().cuda_stream)
+        if first_symbol is None:
+            self._count += y.numel()
+        return rx.cpu().numpy() if host else rx
