@@ -366,6 +366,64 @@ int nrldpc_crc_check_harq_dev(const nrldpc_tb_params* p, const uint8_t* d_c_hat,
                               int32_t* d_ok, int32_t* d_cb_pass, const uint8_t* cbgti_flags, int32_t keep_b_hat,
                               void* stream);
 
+/* ---- mixed transport-block batches: rate recovery and the CRC stage in one launch each -------------------------------------
+ * nrldpc_decode_multi_dev decodes a mix of (BG, Z_c) in a handful of launches; these entry points do the same for the stages either
+ * side of it, for a batch whose transport blocks differ in (BG, A, G, Q_m, rv_id, LBRM, C).  A MIX PLAN is built once from n
+ * parameter blocks and n transport-block counts, is immutable, owns the device-side tables and defines ONE packed layout for every
+ * array of the receive chain; the stage calls take the plan and base pointers only.  nrldpc_decode_multi_dev sits between them
+ * unchanged: its d_llr[i], d_hard[i], d_iters[i] are base + off[i].cw / .c_hat / .cb of the same packed arrays.
+ * Added without a revision bump (NRLDPC_ABI_VERSION stays 6): a binding finds the functions by symbol.
+ *
+ * Layout.  Configuration i's segment of each array is exactly the array the single-configuration call takes; segments follow in the
+ * caller's order; off[0] is 0 in every field; off[i+1].x = round_up(off[i].x + size_i.x, 16) ELEMENTS, so every segment starts 16-byte
+ * aligned for every element type; entry [n] holds the totals (what to allocate).  Rows inside a segment keep whatever alignment G,
+ * N_cb and N_cw give them (odd G with f16 input: rows at odd multiples of 2 bytes).  n_tb[i] == 0 takes no room and does no work;
+ * G == 0 is legal (testbench.m:35).  Gap elements are never read or written.
+ *
+ * Semantics, by equality.  nrldpc_mix_rate_recover_dev leaves in every segment -- output and soft buffer -- bit for bit what
+ *   nrldpc_rate_recover_ex_dev(&p[i], g + off[i].g, in_dtype, n_tb[i], harq ? harq + off[i].harq : NULL, harq_dtype, cw + off[i].cw,
+ *   out_dtype, stream) leaves: the same f32 sums in the same order (repetitions in ascending k, then the buffer), the same clamp
+ *   before any conversion to f16, fillers +inf, filler positions of the buffer untouched; with (F32, F32) it therefore equals
+ *   nrldpc_rate_recover_dev too.  (The environment knobs of the single-configuration launch rule are not read.)
+ * nrldpc_mix_crc_check_dev leaves in b_hat, ok and cb_pass what nrldpc_crc_check_dev leaves per configuration.
+ * One launch per stage call, whatever n; exactly one thread reads and writes each buffer position, no atomics: results are the same
+ * from run to run and do not depend on which configurations share the plan or on how a mix is split into plans.
+ *
+ * Refusals.  nrldpc_mix_layout and nrldpc_mix_create refuse before any device call: for a parameter block the code and text the
+ * single-configuration calls give for it (their parameter checks, E_r / G checks and the CRC length / B checks) with
+ * " (configuration i)" appended; a negative n or n_tb[i], or null arrays with n > 0: NRLDPC_ERR_ARG.  n == 0 is a valid empty plan:
+ * both stage calls on it return NRLDPC_OK without a launch.  Stage calls: a dtype other than F32 / F16 -> NRLDPC_ERR_UNSUPPORTED
+ * (harq_dtype is not read when d_harq is null); a null base pointer whose array is not empty -> NRLDPC_ERR_ARG.
+ *
+ * Concurrency.  The plan's tables are uploaded synchronously by nrldpc_mix_create and never written again: calls in flight on several
+ * streams may share one plan (each with its own arrays).  The stage calls only enqueue: no allocation, copy or synchronisation.
+ *
+ * Out of scope: the HARQ / CBGTI state machine of nrldpc_crc_check_harq_dev, pool variants, the transmit side, the MEX gateway. */
+typedef struct nrldpc_mix* nrldpc_mix_handle;
+
+/* element offsets of configuration i inside the packed arrays; entry [n] holds the totals */
+typedef struct nrldpc_mix_offsets {
+    int64_t g;      /* g_tilde        [n_tb][G]              */
+    int64_t harq;   /* soft buffer    [n_tb][C][N_cb]        */
+    int64_t cw;     /* codeword LLRs  [n_tb*C][ncols*Z]   = d_llr[i]  of nrldpc_decode_multi_dev */
+    int64_t c_hat;  /* hard decisions [n_tb*C][K]         = d_hard[i]                            */
+    int64_t cb;     /* one value per code block [n_tb*C]: d_iters[i], cb_pass                    */
+    int64_t b_hat;  /* [n_tb][B]                                                                 */
+    int64_t tb;     /* one value per transport block [n_tb]: ok                                  */
+} nrldpc_mix_offsets;                       /* sizeof == 56 (the library static_asserts it) */
+
+/* host function, no device: off has n + 1 entries */
+int nrldpc_mix_layout(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, nrldpc_mix_offsets* off);
+
+int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int32_t device_id, nrldpc_mix_handle* out);
+void nrldpc_mix_destroy(nrldpc_mix_handle m);
+
+int nrldpc_mix_rate_recover_dev(nrldpc_mix_handle m, const void* d_g_tilde, int32_t in_dtype,
+                                void* d_harq /* nullable */, int32_t harq_dtype,
+                                void* d_cw_llr, int32_t out_dtype, void* stream);
+int nrldpc_mix_crc_check_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, uint8_t* d_b_hat,
+                             int32_t* d_ok, int32_t* d_cb_pass /* nullable */, void* stream);
+
 /* Transmit-side counterparts (vector generation for the Monte-Carlo harness, plot_BLER_vs_SNR.m:129):
  * nrldpc_crc_attach_dev replaces crc_calculation + code_block_segmentation of the encoder
  * (NRLDPCEncoder.m:70-124): d_a [n_tb][A] bits -> d_c [n_tb*C][K] code blocks (fillers 0), ready for

@@ -98,6 +98,13 @@ def tb_params(p):
     return t
 
 
+class MixOffsets(C.Structure):
+    """nrldpc_mix_offsets: element offsets of one configuration inside the packed arrays of a mix plan (entry [n]: the totals)."""
+    _fields_ = [(k, C.c_int64) for k in ("g", "harq", "cw", "c_hat", "cb", "b_hat", "tb")]
+
+
+MIX_FIELDS = tuple(k for k, _ in MixOffsets._fields_)
+
 EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_dev", "nrldpc_crc_check_harq_dev", "nrldpc_crc_attach_dev", "nrldpc_rate_match_dev", "nrldpc_create", "nrldpc_destroy", "nrldpc_get_dims", "nrldpc_decode", "nrldpc_decode_dev",
            "nrldpc_decode_multi_dev", "nrldpc_quantise_llr", "nrldpc_encode", "nrldpc_encode_dev", "nrldpc_set_timing", "nrldpc_last_kernel_ms",
            "nrldpc_set_index", "nrldpc_lifting_size", "nrldpc_default_rule", "nrldpc_strerror", "nrldpc_last_error",
@@ -106,7 +113,8 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_set_layers", "nrldpc_set_llr_dtype", "nrldpc_last_layers", "nrldpc_count_layers", "nrldpc_pool_set_layers", "nrldpc_pool_decode_packed",
            "nrldpc_decode_packed_layers", "nrldpc_pool_set_timing", "nrldpc_pool_last_kernel_ms", "nrldpc_last_host_phases", "nrldpc_payload_bits_dev",
            "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm", "nrldpc_decode_cw", "nrldpc_decode_cw_dev",
-           "nrldpc_modulate_dev", "nrldpc_demodulate_dev", "nrldpc_rate_recover_ex_dev", "nrldpc_awgn_dev"]
+           "nrldpc_modulate_dev", "nrldpc_demodulate_dev", "nrldpc_rate_recover_ex_dev", "nrldpc_awgn_dev",
+           "nrldpc_mix_layout", "nrldpc_mix_create", "nrldpc_mix_destroy", "nrldpc_mix_rate_recover_dev", "nrldpc_mix_crc_check_dev"]
 
 _lib = None
 
@@ -182,6 +190,13 @@ def load():
     L.nrldpc_demodulate_dev.argtypes = [vp, C.c_int64, i32, i32, C.c_float, vp, vp, i32, vp]
     if hasattr(L, "nrldpc_awgn_dev"):  # added without a revision bump: a library selected with NRLDPC_LIB may lack it
         L.nrldpc_awgn_dev.argtypes = [vp, C.c_int64, C.c_float, vp, C.c_uint64, C.c_uint64, vp, vp]
+    if hasattr(L, "nrldpc_mix_create"):  # the mixed-batch stages, added without a revision bump: a library selected with NRLDPC_LIB may lack them
+        L.nrldpc_mix_layout.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), C.POINTER(MixOffsets)]
+        L.nrldpc_mix_create.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), i32, C.POINTER(vp)]
+        L.nrldpc_mix_destroy.argtypes = [vp]
+        L.nrldpc_mix_destroy.restype = None
+        L.nrldpc_mix_rate_recover_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp]
+        L.nrldpc_mix_crc_check_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     L.nrldpc_crc_attach_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_rate_match_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_pool_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), i32, i32, C.POINTER(vp)]
@@ -549,6 +564,80 @@ def rate_recover_dev(p, d_g_tilde, n_tb, d_harq, d_cw_llr, out_dtype=LLR_F32, st
                           "built from this tree (NRLDPC_LIB selects an older one?)" % lib_path())
     check(L.nrldpc_rate_recover_ex_dev(C.byref(t), _ptr(d_g_tilde), int(in_dtype), int(n_tb), _ptr(d_harq), int(harq_dtype),
                                        _ptr(d_cw_llr), int(out_dtype), C.c_void_p(stream)))
+
+
+def _mix_args(params, n_tb):
+    """(n, TbParams array, int32 array) of a mix: params are NRLDPC parameter objects or TbParams."""
+    params, n_tb = list(params), [int(x) for x in n_tb]
+    if len(params) != len(n_tb):
+        raise NRLDPCError("a mix needs one transport-block count per parameter set (%d sets, %d counts)" % (len(params), len(n_tb)))
+    n = len(params)
+    ts = (TbParams * max(n, 1))()
+    for i, p in enumerate(params):
+        C.memmove(C.byref(ts[i]), C.byref(p if isinstance(p, TbParams) else tb_params(p)), C.sizeof(TbParams))
+    return n, ts, (C.c_int32 * max(n, 1))(*n_tb)
+
+
+def _mix_lib():
+    L = load()
+    if not hasattr(L, "nrldpc_mix_create"):
+        raise NRLDPCError("%s has no nrldpc_mix_create: mixed transport-block batches need a library built from this tree "
+                          "(NRLDPC_LIB selects an older one?)" % lib_path())
+    return L
+
+
+def mix_layout(params, n_tb):
+    """nrldpc_mix_layout: the n + 1 offset records (MixOffsets) of the packed arrays of a mix; entry [n] holds the totals.
+    Host function, no device needed."""
+    n, ts, nt = _mix_args(params, n_tb)
+    off = (MixOffsets * (n + 1))()
+    check(_mix_lib().nrldpc_mix_layout(n, ts, nt, off))
+    return list(off)
+
+
+class MixPlan:
+    """nrldpc_mix_*: an immutable plan for a batch whose transport blocks differ in (BG, A, G, Q_m, rv_id, LBRM, C) -- n parameter
+    sets (NRLDPC objects or TbParams) with n_tb[i] transport blocks each.  It owns the device-side tables and defines one packed
+    layout (.offsets, n + 1 MixOffsets records in elements; entry [n]: the totals) for every array of the receive chain;
+    rate_recover() and crc_check() are one launch each, whatever n.  Streams may share a plan."""
+
+    def __init__(self, params, n_tb, device_id=0):
+        self._h = C.c_void_p()
+        self._lib = L = _mix_lib()
+        self.n, ts, nt = _mix_args(params, n_tb)
+        self.n_tb = [int(x) for x in n_tb]
+        self.device_id = int(device_id)
+        off = (MixOffsets * (self.n + 1))()
+        check(L.nrldpc_mix_layout(self.n, ts, nt, off))
+        self.offsets = list(off)
+        self.params = [ts[i] for i in range(self.n)]
+        self._ts = ts  # (the records above are views of this array)
+        check(L.nrldpc_mix_create(self.n, ts, nt, self.device_id, C.byref(self._h)))
+
+    @property
+    def totals(self):
+        """Elements to allocate for each packed array (MixOffsets)."""
+        return self.offsets[self.n]
+
+    def rate_recover(self, d_g_tilde, d_harq, d_cw_llr, in_dtype=LLR_F32, harq_dtype=LLR_F32, out_dtype=LLR_F32, stream=0):
+        """nrldpc_mix_rate_recover_dev on raw device addresses of the packed arrays (d_harq None: no soft buffer)."""
+        check(self._lib.nrldpc_mix_rate_recover_dev(self._h, _ptr(d_g_tilde), int(in_dtype), _ptr(d_harq), int(harq_dtype),
+                                                    _ptr(d_cw_llr), int(out_dtype), C.c_void_p(stream)))
+
+    def crc_check(self, d_c_hat, d_b_hat, d_ok, d_cb_pass=None, stream=0):
+        """nrldpc_mix_crc_check_dev on raw device addresses of the packed arrays."""
+        check(self._lib.nrldpc_mix_crc_check_dev(self._h, _ptr(d_c_hat), _ptr(d_b_hat), _ptr(d_ok), _ptr(d_cb_pass), C.c_void_p(stream)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.nrldpc_mix_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def crc_check_dev(p, d_c_hat, n_tb, d_b_hat, d_ok, d_cb_pass=None, stream=0):

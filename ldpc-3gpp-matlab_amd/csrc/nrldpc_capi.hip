@@ -37,6 +37,7 @@
 #include "nrldpc_cwout.h"
 #include "nrldpc_modem.h"
 #include "nrldpc_ratematch_ex.h"
+#include "nrldpc_mix.h"
 
 static_assert(sizeof(nrldpc_cw_out) == 32, "nrldpc_cw_out: the size include/nrldpc.h states");
 
@@ -2127,6 +2128,204 @@ int nrldpc_encode(nrldpc_handle h, const uint8_t* info, int32_t batch, uint8_t* 
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(cw, h->s_hard.p, (size_t)batch * ncw, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
+    return NRLDPC_OK;
+}
+
+} // extern "C"
+
+// ---- mixed transport-block batches (nrldpc_mix_*; kernels: nrldpc_mix.hip, tables and mapping: nrldpc_mix.h) -------------------------
+static_assert(sizeof(nrldpc_mix_offsets) == 56, "nrldpc_mix_offsets: the size include/nrldpc.h states");
+static_assert(nrldpc::MIX_FIELDS * sizeof(int64_t) == sizeof(nrldpc_mix_offsets), "one int64 per packed array, in the order of the MIX_* fields");
+
+struct nrldpc_mix {
+    int32_t n = 0, device_id = 0;
+    std::vector<nrldpc_mix_offsets> off; // n + 1
+    int64_t size_g = 0, size_harq = 0, size_cw = 0, size_c_hat = 0, size_b_hat = 0, size_tb = 0; // elements in use (sum over configurations)
+    char* blob = nullptr;                // every device table, one allocation, written once by nrldpc_mix_create
+    nrldpc::MixRmLaunch rm{};
+    nrldpc::MixCrcLaunch crc{};
+};
+
+namespace {
+
+// everything the plan needs, on the host: offsets, records, tables.  No device call.
+struct MixHost {
+    std::vector<nrldpc_mix_offsets> off;
+    std::vector<nrldpc::MixRmRec> rm;
+    std::vector<nrldpc::MixCrcRec> crc;
+    std::vector<int32_t> rm_prefix, tb_prefix, e_tab, off_tab;
+    int64_t used[nrldpc::MIX_FIELDS] = {0, 0, 0, 0, 0, 0, 0};
+    int32_t k_max = 0, c_max = 0;
+};
+
+int mix_fail_at(int rc, int i) {
+    g_err += " (configuration " + std::to_string(i) + ")";
+    return rc;
+}
+
+int mix_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool tables, MixHost& m) {
+    if (n < 0) return fail(NRLDPC_ERR_ARG, "negative configuration count");
+    if (n > 0 && (!p || !n_tb)) return fail(NRLDPC_ERR_ARG, "null array");
+    m.off.assign((size_t)n + 1, nrldpc_mix_offsets{0, 0, 0, 0, 0, 0, 0});
+    m.rm_prefix.assign((size_t)n + 1, 0);
+    m.tb_prefix.assign((size_t)n + 1, 0);
+    if (tables) { m.rm.resize(n); m.crc.resize(n); }
+    int64_t wg = 0, tbs = 0;
+    for (int i = 0; i < n; ++i) {
+        const nrldpc_tb_params* q = p + i;
+        // the checks of the single-configuration calls, with their texts: check_tb_params, fill_rm_blocks, the CRC stage's own
+        int rc = check_tb_params(q);
+        if (rc) return mix_fail_at(rc, i);
+        nrldpc::RmExArgs blocks; // (E_r and the offsets of the code blocks inside a row of g_tilde)
+        rc = fill_rm_blocks(q, 0, blocks);
+        if (rc) return mix_fail_at(rc, i);
+        if ((q->tb_crc_len != 16 && q->tb_crc_len != 24) || (q->cb_crc_len != 0 && q->cb_crc_len != 24))
+            return mix_fail_at(fail(NRLDPC_ERR_UNSUPPORTED, "CRC lengths must be 16/24 (TB) and 0/24 (CB)"), i);
+        if (q->B != q->A + q->tb_crc_len || q->C * (q->K_prime - q->cb_crc_len) != q->B)
+            return mix_fail_at(fail(NRLDPC_ERR_ARG, "B must equal A + L and C*(K' - L_cb)"), i);
+        if (n_tb[i] < 0) return mix_fail_at(fail(NRLDPC_ERR_ARG, "negative batch"), i);
+        const int32_t ncwz = 2 * q->Z + q->N;
+        int64_t s[nrldpc::MIX_FIELDS];
+        nrldpc::mix_sizes(n_tb[i], q->C, q->G, q->N_cb, ncwz, q->K, q->B, s);
+        const int64_t* cur = &m.off[i].g;
+        int64_t* next = &m.off[i + 1].g;
+        for (int k = 0; k < nrldpc::MIX_FIELDS; ++k) { next[k] = nrldpc::mix_round_up(cur[k] + s[k]); m.used[k] += s[k]; }
+        const int32_t per = nrldpc::mix_rm_wg_per_cb(ncwz);
+        wg += (int64_t)n_tb[i] * q->C * per;
+        tbs += n_tb[i];
+        if (wg > INT32_MAX || tbs > INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
+        m.rm_prefix[i + 1] = (int32_t)wg;
+        m.tb_prefix[i + 1] = (int32_t)tbs;
+        if (!tables) continue;
+        if (n_tb[i] > 0) { m.k_max = std::max(m.k_max, q->K); m.c_max = std::max(m.c_max, q->C); }
+        nrldpc::MixRmRec& r = m.rm[i];
+        memset(&r, 0, sizeof r);
+        r.g_off = cur[nrldpc::MIX_G]; r.harq_off = cur[nrldpc::MIX_HARQ]; r.cw_off = cur[nrldpc::MIX_CW];
+        r.n_tb = n_tb[i]; r.C = q->C; r.G = q->G; r.Z = q->Z; r.K = q->K; r.Kp = q->K_prime; r.N = q->N; r.N_cb = q->N_cb;
+        r.k0 = q->k_0; r.Qm = q->Q_m;
+        // the launch rule of launch_rate_recover_ex (nrldpc_ratematch_ex.hip), without its environment knobs
+        const int lo_f = q->K_prime - 2 * q->Z > 0 ? q->K_prime - 2 * q->Z : 0, hi_f = q->K - 2 * q->Z;
+        const int f_hi = hi_f < q->N_cb ? hi_f : q->N_cb;
+        const int P = q->N_cb - (f_hi > lo_f ? f_hi - lo_f : 0);
+        bool repeats = !(q->Q_m == 1 || q->Q_m == 2 || q->Q_m == 4 || q->Q_m == 6 || q->Q_m == 8);
+        for (int b = 0; b < q->C; ++b) repeats = repeats || q->E_r[b] > P;
+        r.form = repeats ? 0 : 1;
+        r.echo = (!repeats && q->Q_m <= 2 && q->N >= 4096) ? 1 : 0;
+        r.e_base = (int32_t)m.e_tab.size();
+        r.wg_per_cb = per;
+        for (int b = 0; b < q->C; ++b) { m.e_tab.push_back(blocks.E[b]); m.off_tab.push_back(blocks.off[b]); }
+        nrldpc::MixCrcRec& c = m.crc[i];
+        memset(&c, 0, sizeof c);
+        c.c_hat_off = cur[nrldpc::MIX_C_HAT]; c.b_hat_off = cur[nrldpc::MIX_B_HAT]; c.cb_off = cur[nrldpc::MIX_CB]; c.tb_off = cur[nrldpc::MIX_TB];
+        c.C = q->C; c.K = q->K; c.Kp = q->K_prime; c.Lcb = q->cb_crc_len; c.A = q->A; c.B = q->B;
+        const int pay = q->K_prime - q->cb_crc_len;
+        make_crc_plan(&c.tb, crc_poly_for(q->tb_crc_len, false), q->tb_crc_len, pay, pay, pay);
+        make_crc_plan(&c.cb, crc_poly_for(24, true), 24, q->K_prime, 0, 0);
+    }
+    return NRLDPC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nrldpc_mix_layout(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, nrldpc_mix_offsets* off) {
+    NRLDPC_API_BEGIN
+    if (n >= 0 && !off) return fail(NRLDPC_ERR_ARG, "null array");
+    MixHost m;
+    int rc = mix_build(n, p, n_tb, false, m);
+    if (rc) return rc;
+    memcpy(off, m.off.data(), m.off.size() * sizeof(nrldpc_mix_offsets));
+    return NRLDPC_OK;
+    NRLDPC_API_END
+}
+
+void nrldpc_mix_destroy(nrldpc_mix_handle m) {
+    if (!m) return;
+    if (m->blob) { DeviceScope scope(m->device_id); (void)hipFree(m->blob); }
+    delete m;
+}
+
+int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int32_t device_id, nrldpc_mix_handle* out) {
+    NRLDPC_API_BEGIN
+    if (!out) return fail(NRLDPC_ERR_ARG, "null out");
+    *out = nullptr;
+    MixHost mh;
+    int rc = mix_build(n, p, n_tb, true, mh);
+    if (rc) return rc;
+    const bool empty = n == 0 || mh.tb_prefix[n] == 0; // an empty plan: no tables, no launches, no device call at all
+    if (!empty) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+            return fail(NRLDPC_ERR_HIP, "no HIP device available (this library has no CPU path)");
+        if (device_id < 0 || device_id >= ndev) return fail(NRLDPC_ERR_ARG, "device_id out of range");
+    }
+    nrldpc_mix* m = new (std::nothrow) nrldpc_mix();
+    if (!m) return fail(NRLDPC_ERR_NOMEM, "host allocation failed");
+    m->n = n; m->device_id = device_id; m->off = mh.off;
+    m->size_g = mh.used[nrldpc::MIX_G]; m->size_harq = mh.used[nrldpc::MIX_HARQ]; m->size_cw = mh.used[nrldpc::MIX_CW];
+    m->size_c_hat = mh.used[nrldpc::MIX_C_HAT]; m->size_b_hat = mh.used[nrldpc::MIX_B_HAT]; m->size_tb = mh.used[nrldpc::MIX_TB];
+    m->rm.n = n; m->rm.n_wg = mh.rm_prefix[n];
+    m->crc.n = n; m->crc.n_tb_total = mh.tb_prefix[n];
+    m->crc.k_max = mh.k_max; m->crc.c_max = mh.c_max; m->crc.waves = mh.c_max < 4 ? (mh.c_max < 1 ? 1 : mh.c_max) : 4;
+    if (empty) { *out = m; return NRLDPC_OK; }
+    // one allocation, every table at a multiple of 16 bytes, uploaded synchronously and never written again
+    auto pad16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_rm = 0, o_crc = o_rm + pad16(mh.rm.size() * sizeof(nrldpc::MixRmRec)), o_rp = o_crc + pad16(mh.crc.size() * sizeof(nrldpc::MixCrcRec)),
+                 o_tp = o_rp + pad16(mh.rm_prefix.size() * 4), o_e = o_tp + pad16(mh.tb_prefix.size() * 4), o_o = o_e + pad16(mh.e_tab.size() * 4),
+                 total = o_o + pad16(mh.off_tab.size() * 4);
+    std::vector<char> img(total, 0);
+    memcpy(img.data() + o_rm, mh.rm.data(), mh.rm.size() * sizeof(nrldpc::MixRmRec));
+    memcpy(img.data() + o_crc, mh.crc.data(), mh.crc.size() * sizeof(nrldpc::MixCrcRec));
+    memcpy(img.data() + o_rp, mh.rm_prefix.data(), mh.rm_prefix.size() * 4);
+    memcpy(img.data() + o_tp, mh.tb_prefix.data(), mh.tb_prefix.size() * 4);
+    memcpy(img.data() + o_e, mh.e_tab.data(), mh.e_tab.size() * 4);
+    memcpy(img.data() + o_o, mh.off_tab.data(), mh.off_tab.size() * 4);
+    DeviceScope scope(device_id);
+    hipError_t e = scope.err;
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->blob), total);
+    if (e == hipSuccess) e = hipMemcpy(m->blob, img.data(), total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { nrldpc_mix_destroy(m); return hipfail(e, "mix plan tables"); }
+    m->rm.recs = reinterpret_cast<const nrldpc::MixRmRec*>(m->blob + o_rm);
+    m->crc.recs = reinterpret_cast<const nrldpc::MixCrcRec*>(m->blob + o_crc);
+    m->rm.prefix = reinterpret_cast<const int32_t*>(m->blob + o_rp);
+    m->crc.prefix = reinterpret_cast<const int32_t*>(m->blob + o_tp);
+    m->rm.e_tab = reinterpret_cast<const int32_t*>(m->blob + o_e);
+    m->rm.off_tab = reinterpret_cast<const int32_t*>(m->blob + o_o);
+    *out = m;
+    return NRLDPC_OK;
+    NRLDPC_API_END
+}
+
+int nrldpc_mix_rate_recover_dev(nrldpc_mix_handle m, const void* d_g_tilde, int32_t in_dtype, void* d_harq, int32_t harq_dtype,
+                                void* d_cw_llr, int32_t out_dtype, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    auto known = [](int32_t d) { return d == NRLDPC_LLR_F32 || d == NRLDPC_LLR_F16; };
+    if (!known(in_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "in_dtype must be f32 or f16");
+    if (d_harq && !known(harq_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "harq_dtype must be f32 or f16");
+    if (!known(out_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "out_dtype must be f32 or f16");
+    if ((m->size_cw > 0 && !d_cw_llr) || (m->size_g > 0 && !d_g_tilde)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->rm.n_wg == 0) return NRLDPC_OK;
+    nrldpc::MixRmLaunch a = m->rm; // (a copy: calls in flight on several streams share the plan, never a launch block)
+    a.g = d_g_tilde; a.harq = d_harq; a.out = d_cw_llr;
+    a.in_f16 = in_dtype == NRLDPC_LLR_F16; a.harq_f16 = d_harq && harq_dtype == NRLDPC_LLR_F16; a.out_f16 = out_dtype == NRLDPC_LLR_F16;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_rate_recover(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix rate-recovery kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_crc_check_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, uint8_t* d_b_hat, int32_t* d_ok, int32_t* d_cb_pass, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if ((m->size_c_hat > 0 && !d_c_hat) || (m->size_b_hat > 0 && !d_b_hat) || (m->size_tb > 0 && !d_ok)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->crc.n_tb_total == 0) return NRLDPC_OK;
+    nrldpc::MixCrcLaunch a = m->crc;
+    a.c_hat = d_c_hat; a.b_hat = d_b_hat; a.ok = d_ok; a.cb_pass = d_cb_pass;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_crc_check(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix CRC kernel launch");
     return NRLDPC_OK;
 }
 

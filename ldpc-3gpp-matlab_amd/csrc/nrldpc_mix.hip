@@ -1,0 +1,324 @@
+// nrldpc_mix.hip -- rate recovery and the CRC stage for a MIX of transport-block configurations in one launch each
+// (nrldpc_mix_rate_recover_dev, nrldpc_mix_crc_check_dev; semantics: include/nrldpc.h).
+//
+// Both kernels are table driven.  The per-configuration records (scalar parameters, E_r and its offsets, the two CRC plans) and a
+// prefix table over the work items live in device memory, uploaded once by nrldpc_mix_create and never written again; a
+// workgroup finds its configuration by a binary search of the prefix table (nrldpc_mix.h: mix_find, mix_rm_work), so everything
+// that selects a code path -- configuration, form, element types, Q_m -- is workgroup-uniform.  The number of launches does not
+// depend on the number of configurations: one per stage.
+//
+// Rate recovery is the gather of nrldpc_ratematch_ex.hip -- four neighbouring positions of a code block's decoder input per lane,
+// the same index arithmetic, the same f32 sums in the same order (repetitions in ascending k, then the buffer), the same clamp
+// before any conversion to f16 -- and leaves bit for bit what nrldpc_rate_recover_ex_dev leaves in every segment.  A segment of
+// a packed array starts 16 elements aligned, its rows do not (odd G, odd N_cb): every access wider than one element is taken by
+// a test on the address it would use.  Every buffer position is read and written by exactly one thread; no atomics.
+//
+// The CRC stage is the wave-per-code-block kernel of nrldpc_crc.hip (LDS staging, per-lane bit-serial register, GF(2) combine
+// tree, Horner fold of the segment remainders for the transport-block CRC) with the plans read from the record.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+
+#include "nrldpc_mix.h"
+#include "nrldpc_wave.h"
+
+namespace nrldpc {
+namespace {
+
+typedef _Float16 half_t;
+
+// ---- element helpers: the rules of nrldpc_ratematch_ex.hip ---------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ T narrow(float v) {
+    if constexpr (std::is_same<T, float>::value) return v;
+    else return (half_t)fminf(fmaxf(v, -65504.0f), 65504.0f);
+}
+template <typename T> __device__ __forceinline__ T filler_mark() { return (T)__builtin_inff(); }
+
+template <typename T> struct Quad;
+template <> struct Quad<float> { typedef float __attribute__((ext_vector_type(4), aligned(4))) type; };
+template <> struct Quad<half_t> { typedef half_t __attribute__((ext_vector_type(4), aligned(4))) type; };
+// a multi-dword global access needs dword alignment: f32 always has it, f16 by the address
+template <typename T> __device__ __forceinline__ bool quad_ok(const T* p) { return sizeof(T) == 4 || (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+template <typename T> __device__ __forceinline__ void load4(const T* p, T (&v)[4]) {
+    if (quad_ok(p)) {
+        const typename Quad<T>::type w = *reinterpret_cast<const typename Quad<T>::type*>(p);
+        v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+    } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = p[t];
+    }
+}
+template <typename T> __device__ __forceinline__ void store4(T* p, const T (&v)[4]) {
+    if (quad_ok(p)) {
+        typename Quad<T>::type w;
+        w.x = v[0]; w.y = v[1]; w.z = v[2]; w.w = v[3];
+        *reinterpret_cast<typename Quad<T>::type*>(p) = w;
+    } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) p[t] = v[t];
+    }
+}
+
+// NRLDPCDecoder.m:236-239 for one position: the buffer takes sum + buffer (one f32 add) in its own element type and the decoder's
+// LLR is what the buffer now holds
+template <typename HbT> __device__ __forceinline__ float combine(float sum, HbT& h) {
+    h = narrow<HbT>(sum + (float)h);
+    return (float)h;
+}
+
+// The tail for the four positions pos0 .. pos0+3 of a code block's decoder input (p0 = pos0 - 2Z in d): val[t] = what this
+// transmission delivers, fill[t] = filler (+inf), inb[t] = a non-filler position of the circular buffer, keep[t] = the position
+// receives nothing and the configuration leaves such buffer entries as they are (MixRmRec::echo): read, not written.
+template <typename HbT, typename OutT>
+__device__ __forceinline__ void finish4(HbT* hb, OutT* out, int pos0, int p0, int ncwz, float (&val)[4], const bool (&fill)[4], const bool (&inb)[4],
+                                        const bool (&keep)[4]) {
+    if (hb) {
+        if (inb[0] && inb[1] && inb[2] && inb[3] && !(keep[0] || keep[1] || keep[2] || keep[3])) {
+            HbT h[4];
+            load4(hb + p0, h);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) val[t] = combine(val[t], h[t]);
+            store4(hb + p0, h);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (inb[t]) {
+                    HbT h = hb[p0 + t];
+                    if (keep[t]) {
+                        val[t] = (float)h;
+                    } else {
+                        val[t] = combine(val[t], h);
+                        hb[p0 + t] = h;
+                    }
+                }
+        }
+    }
+    OutT o[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) o[t] = fill[t] ? filler_mark<OutT>() : narrow<OutT>(val[t]);
+    if (pos0 + 3 < ncwz) {
+        store4(out + pos0, o);
+    } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (pos0 + t < ncwz) out[pos0 + t] = o[t];
+    }
+}
+
+} // namespace
+
+// ---- rate recovery ---------------------------------------------------------------------------------------------------------------
+template <typename InT, typename HbT, typename OutT>
+__global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const MixRmLaunch a) {
+    const MixRmWork w = mix_rm_work(a.prefix, a.recs, a.n, (int)blockIdx.x);
+    const MixRmRec& c = a.recs[w.cfg];
+    const int blk = w.blk; // tb * C + r
+    const int C = c.C, Z = c.Z, N_cb = c.N_cb, Qm = c.Qm;
+    const int tb = blk / C, r = blk - tb * C;
+    const int ncwz = 2 * Z + c.N;
+    const int lane = threadIdx.x & 63;
+    const int tile0 = w.tile0 + ((int)threadIdx.x >> 6) * MIX_RM_TILE;
+    if (tile0 >= ncwz) return;
+    const int lo_f = c.Kp - 2 * Z > 0 ? c.Kp - 2 * Z : 0, hi_f = c.K - 2 * Z; // fillers (NRLDPCDecoder.m:224)
+    const int f_hi = hi_f < N_cb ? hi_f : N_cb;
+    const int F = f_hi > lo_f ? f_hi - lo_f : 0;
+    const int P = N_cb - F;
+    auto nf = [&](int x) { int d = x - lo_f; d = d < 0 ? 0 : (d > F ? F : d); return x - d; };
+    const int nfk0 = nf(c.k0);
+    const int E = a.e_tab[c.e_base + r];
+    const int rows = E > 0 ? E / Qm : 1;
+    const InT* f = static_cast<const InT*>(a.g) + c.g_off + (int64_t)tb * c.G + a.off_tab[c.e_base + r];
+    HbT* hb = a.harq ? static_cast<HbT*>(a.harq) + c.harq_off + (int64_t)blk * N_cb : nullptr;
+    OutT* out = static_cast<OutT*>(a.out) + c.cw_off + (int64_t)blk * ncwz;
+    const bool echo = hb && c.echo;
+    if (c.form == 0) {
+        // the general gather: repetitions summed in ascending k (:229-231), then the buffer
+        const int Pq = P / rows, Pr = P - Pq * rows; // a repetition is P positions of e further on
+#pragma unroll
+        for (int s = 0; s < MIX_RM_SWEEPS; ++s) {
+            const int pos0 = tile0 + s * 256 + 4 * lane;
+            if (pos0 >= ncwz) break;
+            float val[4];
+            bool fill[4], inb[4];
+            const bool keep[4] = {false, false, false, false};
+            // q: index among the buffer's non-filler positions counted from k_0; e index q = i*rows + j
+            int q = -1, j = 0, i = 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int p = pos0 + t - 2 * Z;
+                val[t] = 0.0f;
+                fill[t] = p >= lo_f && p < hi_f;
+                inb[t] = p >= 0 && !fill[t] && p < N_cb;
+                if (inb[t]) {
+                    if (q < 0) {
+                        q = nf(p) - nfk0;
+                        if (q < 0) q += P;
+                        for (int m = 1; m < Qm; ++m) i += (q >= m * rows); // q / rows when q < E = Qm * rows
+                        j = q - i * rows;
+                    }
+                    if (q < E) { // (a position that receives nothing does not touch g_tilde)
+                        float v = (float)f[j * Qm + i];
+                        int jj = j, ii = i;
+                        for (int k = q + P; k < E; k += P) {
+                            jj += Pr; ii += Pq;
+                            if (jj >= rows) { jj -= rows; ++ii; }
+                            v += (float)f[jj * Qm + ii];
+                        }
+                        val[t] = v;
+                    }
+                    ++q; ++j;
+                    if (j == rows) { j = 0; ++i; }
+                    if (q == P) { q = 0; j = 0; i = 0; }
+                }
+            }
+            finish4(hb, out, pos0, pos0 - 2 * Z, ncwz, val, fill, inb, keep);
+        }
+        return;
+    }
+    // no repetition: a position takes exactly one e(k) or none
+#pragma unroll
+    for (int s = 0; s < MIX_RM_SWEEPS; ++s) {
+        const int pos0 = tile0 + s * 256 + 4 * lane;
+        if (pos0 >= ncwz) break;
+        float val[4];
+        bool fill[4], inb[4], live[4], keep[4];
+        int idx[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int p = pos0 + t - 2 * Z;
+            fill[t] = p >= lo_f && p < hi_f;
+            inb[t] = p >= 0 && p < N_cb && !fill[t];
+            int d = p - lo_f;
+            d = d < 0 ? 0 : (d > F ? F : d);
+            int q = p - d - nfk0;
+            q += q < 0 ? P : 0;
+            int i = 0;
+            for (int m = 1; m < Qm; ++m) i += (q >= m * rows);
+            const int j = q - i * rows;
+            live[t] = inb[t] && q < E;
+            keep[t] = echo && inb[t] && !live[t];
+            idx[t] = live[t] ? j * Qm + i : 0;
+        }
+        // predicated: a position that receives nothing must not touch g_tilde at all -- for a trailing code block with E_r == 0
+        // f already points one past the transport block's LLRs
+#pragma unroll
+        for (int t = 0; t < 4; ++t) val[t] = live[t] ? (float)f[idx[t]] : 0.0f;
+        finish4(hb, out, pos0, pos0 - 2 * Z, ncwz, val, fill, inb, keep);
+    }
+}
+
+hipError_t launch_mix_rate_recover(const MixRmLaunch& a, hipStream_t stream) {
+    if (a.n_wg <= 0) return hipSuccess;
+    const dim3 grid(a.n_wg), block(256);
+    auto with_out = [&](auto in, auto hb) {
+        typedef decltype(in) InT;
+        typedef decltype(hb) HbT;
+        if (a.out_f16) hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, half_t>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, float>), grid, block, 0, stream, a);
+    };
+    auto with_hb = [&](auto in) {
+        if (a.harq && a.harq_f16) with_out(in, half_t{});
+        else with_out(in, float{}); // (without a buffer its type is never used)
+    };
+    if (a.in_f16) with_hb(half_t{});
+    else with_hb(float{});
+    return hipGetLastError();
+}
+
+// ---- CRC stage -------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// v * M over GF(2), M = 24 columns (zero beyond the CRC length) in device memory; every lane calls this (wave-uniform control flow):
+// lane b fetches column b once and the 24 columns are then broadcast with v_readlane
+__device__ __forceinline__ uint32_t gf2_apply(const uint32_t* M, uint32_t v) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t mine = M[lane < 24 ? lane : 0];
+    uint32_t o = 0;
+#pragma unroll
+    for (int b = 0; b < 24; ++b) o ^= (0u - ((v >> b) & 1u)) & (uint32_t)__builtin_amdgcn_readlane((int)mine, b);
+    return o;
+}
+
+// CRC remainder of `len` bits (one per byte, in LDS) by one wave; every lane returns the result.
+// pl.chunk bits per lane with 64 * chunk >= len; the shortfall acts as leading zeros.
+__device__ __forceinline__ uint32_t wave_crc(const uint8_t* bits, int len, const CrcPlan& pl) {
+    const int lane = threadIdx.x & 63;
+    const int chunk = pl.chunk;
+    const int pad = 64 * chunk - len;
+    const uint32_t top = 1u << (pl.L - 1), mask = (1u << pl.L) - 1u, poly = pl.poly & mask;
+    uint32_t reg = 0;
+    const int i0 = lane * chunk - pad;
+#pragma unroll 4
+    for (int i = i0 < 0 ? 0 : i0; i < i0 + chunk; ++i) {
+        const uint32_t fb = ((reg & top) ? 1u : 0u) ^ (bits[i] & 1u);
+        reg = (reg << 1) & mask;
+        reg ^= fb ? poly : 0u;
+    }
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        const uint32_t right = __shfl_down(reg, 1 << s, 64);
+        reg = gf2_apply(pl.shiftmat[s], reg) ^ right;
+    }
+    return __shfl(reg, 0, 64);
+}
+
+__host__ __device__ __forceinline__ int mix_row_capacity(int K) { return ((K + 15) & ~15) + 48; }
+
+} // namespace
+
+// one workgroup per transport block, one wave per code block (waves loop when C exceeds the workgroup's waves)
+__global__ __launch_bounds__(256) void nrldpc_mix_crc_check_kernel(const MixCrcLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6, lane = threadIdx.x & 63;
+    const int cfg = mix_find(a.prefix, a.n, (int)blockIdx.x);
+    const MixCrcRec& c = a.recs[cfg];
+    const int tb = (int)blockIdx.x - a.prefix[cfg];
+    const int C = c.C, K = c.K, Kp = c.Kp;
+    const int cap = mix_row_capacity(a.k_max); // one stride for every configuration: the carve-up below stays 16-byte aligned
+    uint8_t* base = reinterpret_cast<uint8_t*>(lds) + (size_t)wave * cap;
+    int* cb_fail = reinterpret_cast<int*>(lds + (size_t)nw * cap);  // [c_max]
+    uint32_t* part = reinterpret_cast<uint32_t*>(cb_fail + a.c_max); // [c_max] TB-polynomial remainder per segment
+    const uint8_t* chat = a.c_hat + c.c_hat_off + (int64_t)tb * C * K;
+    uint8_t* b_hat = a.b_hat + c.b_hat_off + (int64_t)tb * c.B;
+    const int pay = Kp - c.Lcb; // payload bits per code block
+    for (int r = wave; r < C; r += nw) {
+        wave_lds_sync(); // previous round's readers are done with the row
+        const uint8_t* row = stage_row(base, chat + (size_t)r * K, Kp);
+        wave_lds_sync();
+        int fail = 0;
+        if (C > 1) fail = wave_crc(row, Kp, c.cb) != 0; // NRLDPCDecoder.m:298-301
+        uint32_t p;
+        if (!fail) {
+            p = wave_crc(row, pay, c.tb);
+            store_row(b_hat + (size_t)r * pay, row, pay); // :303-309 payload copy
+        } else {                                          // :289: b_hat = zeros(B,1)
+            p = 0;
+            uint8_t* z = b_hat + (size_t)r * pay;
+            for (int i = lane; i < pay; i += 64) z[i] = 0;
+        }
+        if (lane == 0) { cb_fail[r] = fail; part[r] = p; }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        uint32_t reg = 0; // :336 over b_hat = segment 0 || ... || segment C-1
+        for (int r = 0; r < C; ++r) reg = gf2_apply(c.tb.horner, reg) ^ part[r];
+        int any_cb = 0;   // :337 any(~code_block_CRC_passed)
+        for (int r = lane; r < C; r += 64) {
+            const int pass = cb_fail[r] ? 0 : 1;
+            if (a.cb_pass) a.cb_pass[c.cb_off + (int64_t)tb * C + r] = pass;
+            any_cb |= !pass;
+        }
+        any_cb = __any(any_cb);
+        if (lane == 0) a.ok[c.tb_off + tb] = (reg != 0 || any_cb) ? 0 : 1; // :337-339
+    }
+}
+
+hipError_t launch_mix_crc_check(const MixCrcLaunch& a, hipStream_t stream) {
+    if (a.n_tb_total <= 0) return hipSuccess;
+    const size_t lds = (size_t)a.waves * mix_row_capacity(a.k_max) + 8 * (size_t)a.c_max + 16;
+    hipLaunchKernelGGL(nrldpc_mix_crc_check_kernel, dim3(a.n_tb_total), dim3(64 * a.waves), lds, stream, a);
+    return hipGetLastError();
+}
+
+} // namespace nrldpc

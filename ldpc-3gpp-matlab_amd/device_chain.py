@@ -6,7 +6,7 @@ with no host loop and no PCIe traffic in between.  torch is used for device memo
 """
 import numpy as np
 
-from ._capi import LLR_F16, LLR_F32, Codec, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
+from ._capi import LLR_F16, LLR_F32, MIX_FIELDS, Codec, MixPlan, MultiCall, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
 from .nrldpc import NRLDPC
 
 
@@ -148,6 +148,115 @@ class DeviceDecodeChain:
         crc_check_harq_dev(t, c_hat.data_ptr(), n_tb, self.b_hat.data_ptr(), ok.data_ptr(), self.cb_pass.data_ptr(),
                            d.flags, self.I_HARQ != 0, stream)
         return self.b_hat[:, : d.A].clone(), ok != 0, iters.view(n_tb, C_)
+
+
+class MixedDecodeChain:
+    """The receive chain for a MIX of configurations: n parameter sets (NRLDPC objects) with n_tb[i] transport blocks each, from
+    demodulator LLRs to b_hat in a number of launches that does not depend on n -- mix rate recovery (one launch), the mixed-batch
+    decoder (nrldpc_decode_multi_dev: a handful), the mix CRC stage (one launch).  Every array is PACKED: configuration i's segment
+    starts at plan.offsets[i].<field> elements and is exactly the array DeviceDecodeChain uses for that configuration;
+    views() / pack() convert.  One codec per configuration (its layer count from active_layers() when prune_layers) and one
+    MultiCall, both built once.  The chain keeps no HARQ state (I_HARQ = 0, no CBGTI state machine); a soft buffer is reachable at
+    the MixPlan level (plan.rate_recover with d_harq)."""
+
+    _SHAPES = {"g": lambda t, n: (n, t.G), "harq": lambda t, n: (n, t.C, t.N_cb), "cw": lambda t, n: (n * t.C, 2 * t.Z + t.N),
+               "c_hat": lambda t, n: (n * t.C, t.K), "cb": lambda t, n: (n, t.C), "b_hat": lambda t, n: (n, t.B), "tb": lambda t, n: (n,)}
+
+    def __init__(self, params, n_tb, iterations=50, alpha=None, beta=0.0, llr_scale=0, prune_layers=True, llr_dtype=None,
+                 algorithm="min-sum", device_id=0):
+        algorithm_code(algorithm)  # UnsupportedParameters for an unknown name, before any device work
+        import torch
+        self.torch = torch
+        params = list(params)
+        for p in params:
+            p.validate()
+        self.params, self.n_tb = params, [int(x) for x in n_tb]
+        self.algorithm = algorithm
+        self.llr_dtype = np.dtype(llr_dtype if llr_dtype is not None else np.float32 if algorithm == "sum-product" else np.float16)
+        if self.llr_dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+            raise UnsupportedParameters("llr_dtype should be numpy float32 or float16, not %r." % (llr_dtype,))
+        self.dev = torch.device("cuda", device_id)
+        self.device_id = device_id
+        self.plan = MixPlan(params, self.n_tb, device_id=device_id)
+        self.codecs = []
+        try:
+            for p in params:
+                rows = 46 if p.BG == 1 else 42
+                self.codecs.append(Codec(p.BG, p.Z_c, max_iter=int(iterations), n_layers=p.active_layers() if prune_layers else rows,
+                                         early_term=True, alpha=alpha or 0.0, beta=beta, llr_scale=llr_scale, llr_dtype=self.llr_dtype,
+                                         device_id=device_id, algorithm=algorithm))
+            tot, off = self.plan.totals, self.plan.offsets
+            tdt = torch.float16 if self.llr_dtype == np.float16 else torch.float32
+            # the chain's own packed arrays, allocated once (gaps stay zero: the kernels never touch them)
+            self.cw_llr = torch.zeros(tot.cw, dtype=tdt, device=self.dev)
+            self.c_hat = torch.zeros(tot.c_hat, dtype=torch.uint8, device=self.dev)
+            self.iters = torch.zeros(tot.cb, dtype=torch.int32, device=self.dev)
+            self.b_hat = torch.zeros(tot.b_hat, dtype=torch.uint8, device=self.dev)
+            self.ok = torch.zeros(tot.tb, dtype=torch.int32, device=self.dev)
+            n = len(params)
+            self._multi = MultiCall(self.codecs, [self.cw_llr.data_ptr() + off[i].cw * self.llr_dtype.itemsize for i in range(n)],
+                                    [self.n_tb[i] * params[i].C for i in range(n)], [self.c_hat.data_ptr() + off[i].c_hat for i in range(n)],
+                                    [self.iters.data_ptr() + 4 * off[i].cb for i in range(n)]) if n else None
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for c in getattr(self, "codecs", []):
+            c.close()
+        self.codecs = []
+        self._multi = None
+        if getattr(self, "plan", None) is not None:
+            self.plan.close()
+
+    def views(self, packed, field):
+        """The per-configuration views of a packed tensor: field is one of "g", "harq", "cw", "c_hat", "cb" (iters, cb_pass), "b_hat",
+        "tb" (ok); view i has the shape of the single-configuration array ([n_tb][G], [n_tb][C][N_cb], [n_tb*C][N_cw], [n_tb*C][K],
+        [n_tb][C], [n_tb][B], [n_tb])."""
+        if field not in MIX_FIELDS:
+            raise NRLDPCError("unknown field %r (one of %s)" % (field, ", ".join(MIX_FIELDS)))
+        flat = packed.reshape(-1)
+        if flat.numel() < getattr(self.plan.totals, field):
+            raise NRLDPCError("the packed %s array should hold at least %d elements." % (field, getattr(self.plan.totals, field)))
+        out = []
+        for i, t in enumerate(self.plan.params):
+            shape = self._SHAPES[field](t, self.n_tb[i])
+            o = getattr(self.plan.offsets[i], field)
+            out.append(flat[o: o + int(np.prod(shape, dtype=np.int64))].view(shape))
+        return out
+
+    def pack(self, tensors, field):
+        """A packed tensor (gaps zero) from one tensor per configuration, each of the single-configuration shape for `field`."""
+        tensors = list(tensors)
+        if len(tensors) != len(self.params):
+            raise NRLDPCError("one tensor per configuration expected (%d), got %d." % (len(self.params), len(tensors)))
+        dt = tensors[0].dtype if tensors else self.torch.float32
+        packed = self.torch.zeros(getattr(self.plan.totals, field), dtype=dt, device=self.dev)
+        for v, x in zip(self.views(packed, field), tensors):
+            if tuple(x.shape) != tuple(v.shape) or x.dtype != dt:
+                raise NRLDPCError("a tensor of shape %s and type %s expected for field %r, got %s %s." % (tuple(v.shape), dt, field, tuple(x.shape), x.dtype))
+            v.copy_(x)
+        return packed
+
+    def step(self, g_tilde_packed):
+        """g_tilde_packed: the packed float32 or float16 demodulator LLRs on the device (plan.totals.g elements; pack(..., "g")).
+        Returns (b_hat_packed uint8, ok int32, iters int32): the chain's own packed device arrays, valid until the next step (clone
+        what must live longer); views(b_hat_packed, "b_hat")[i][:, :A] is a_hat of configuration i, views(ok, "tb")[i] its flags
+        (0 where the reference returns []), views(iters, "cb")[i] its iteration counts [n_tb][C]."""
+        torch = self.torch
+        g = g_tilde_packed
+        if g.dim() != 1 or g.dtype not in (torch.float32, torch.float16) or not g.is_cuda or not g.is_contiguous() or g.numel() < self.plan.totals.g:
+            raise NRLDPCError("g_tilde should be a contiguous 1-D float32 or float16 device tensor of at least %d elements." % self.plan.totals.g)
+        if g.device != self.dev:
+            raise NRLDPCError("g_tilde lives on %s, this chain on %s." % (g.device, self.dev))
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            self.plan.rate_recover(g.data_ptr() if g.numel() else None, None, self.cw_llr.data_ptr(), in_dtype=LLR_F16 if g.dtype == torch.float16 else LLR_F32,
+                                   out_dtype=LLR_F16 if self.llr_dtype == np.float16 else LLR_F32, stream=stream)
+            if self._multi is not None:
+                self._multi(stream)
+            self.plan.crc_check(self.c_hat.data_ptr(), self.b_hat.data_ptr(), self.ok.data_ptr(), None, stream=stream)
+        return self.b_hat, self.ok, self.iters
 
 
 class DeviceEncodeChain:
