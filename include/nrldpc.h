@@ -398,7 +398,37 @@ int nrldpc_crc_check_harq_dev(const nrldpc_tb_params* p, const uint8_t* d_c_hat,
  * Concurrency.  The plan's tables are uploaded synchronously by nrldpc_mix_create and never written again: calls in flight on several
  * streams may share one plan (each with its own arrays).  The stage calls only enqueue: no allocation, copy or synchronisation.
  *
- * Out of scope: the HARQ / CBGTI state machine of nrldpc_crc_check_harq_dev, pool variants, the transmit side, the MEX gateway. */
+ * HARQ and CBGTI.  nrldpc_mix_rate_recover_harq_dev and nrldpc_mix_crc_check_harq_dev (below the plain calls, which are unchanged in
+ * bits and in code path) carry the reference decoder's state machine -- d_tilde_buffer, b_hat_buffer, the sticky
+ * code_block_CRC_passed, CBGTI_flags and reset (NRLDPCDecoder.m:236-239, 286-316, 337, 343-356) -- per TRANSPORT BLOCK of the mix.
+ * Added without a revision bump as well.  Two flag arrays, both on the device (per-configuration host arrays do not fit a kernel
+ * argument block at n ~ 100), both nullable:
+ *   d_new    one byte per transport block in the packed `tb` layout (configuration i's flags start at element off[i].tb); non-zero =
+ *            this transport block starts a new HARQ process in this step; NULL = none does.
+ *   d_cbgti  one byte per code block in the packed `cb` layout (at off[i].cb + tb*C + r): the CBGTI_flags of NRLDPC.m:471-477, per
+ *            transport block; NULL = all 1.
+ * Rate recovery: a transport block whose flag is 0 gets, in every segment, bit for bit what nrldpc_mix_rate_recover_dev leaves with the
+ *   same buffer.  For a flagged one, output and buffer at every non-filler position are bit for bit what nrldpc_rate_recover_ex_dev
+ *   leaves on a buffer that held +0.0 in every position of that block's [C][N_cb] rows: a position that receives nothing ends as +0,
+ *   a delivered -0.0 ends as +0 too (-0 + +0), the same clamp before any conversion to f16.  The old contents of a flagged block's
+ *   rows are never read (NaN or stale data there reaches nothing), so starting a new process costs no memset pass and no second
+ *   launch.  Filler positions of the buffer are never touched, flagged or not.  d_new == NULL equals nrldpc_mix_rate_recover_dev bit
+ *   for bit.  d_harq is required whenever the plan's harq total is non-zero.
+ * CRC stage: for a transport block with new = 0, b_hat, ok and cb_pass are what nrldpc_crc_check_harq_dev(&p[i], ..., n_tb = 1,
+ *   cbgti_flags = that block's C flags, keep_b_hat = 1) leaves on that block's rows -- a code block is taken over only when its CRC
+ *   holds (C > 1) and its flag is 1; segments not taken over keep what they held and enter the transport-block CRC with those bits;
+ *   cb_pass is ORed with its old value.  For new = 1: the same call with keep_b_hat = 0 on a cb_pass row zeroed first -- the
+ *   reference's reset() followed by a step, for that transport block alone.  When all transport blocks of a configuration share flags
+ *   and new, the call equals one nrldpc_crc_check_harq_dev per configuration.  d_cb_pass is required (in/out): a null one with a
+ *   non-empty cb array -> NRLDPC_ERR_ARG with the single call's text.
+ * Both: one launch per call whatever n, one thread per buffer position, no atomics, results independent of how a mix is split into
+ *   plans, gap elements never read or written, enqueue only; null base pointers of non-empty arrays and bad dtypes are refused as in
+ *   the plain calls (harq_dtype always: the buffer is required), before any device call; on the empty plan both return NRLDPC_OK
+ *   without a launch.
+ * rv_id.  A plan stays immutable.  rv_id only moves k_0, and no field of nrldpc_mix_layout depends on it: a HARQ receiver holds one
+ *   plan per redundancy version (per distinct tuple of rv_ids, at most a handful) over the SAME packed arrays.
+ *
+ * Out of scope: pool variants, the transmit side, the MEX gateway, a G that changes between retransmissions. */
 typedef struct nrldpc_mix* nrldpc_mix_handle;
 
 /* element offsets of configuration i inside the packed arrays; entry [n] holds the totals */
@@ -423,6 +453,14 @@ int nrldpc_mix_rate_recover_dev(nrldpc_mix_handle m, const void* d_g_tilde, int3
                                 void* d_cw_llr, int32_t out_dtype, void* stream);
 int nrldpc_mix_crc_check_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, uint8_t* d_b_hat,
                              int32_t* d_ok, int32_t* d_cb_pass /* nullable */, void* stream);
+
+/* the HARQ / CBGTI forms ("HARQ and CBGTI" above) */
+int nrldpc_mix_rate_recover_harq_dev(nrldpc_mix_handle m, const void* d_g_tilde, int32_t in_dtype,
+                                     void* d_harq, int32_t harq_dtype, void* d_cw_llr, int32_t out_dtype,
+                                     const uint8_t* d_new /* nullable */, void* stream);
+int nrldpc_mix_crc_check_harq_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, uint8_t* d_b_hat, int32_t* d_ok,
+                                  int32_t* d_cb_pass /* required, in/out */, const uint8_t* d_cbgti /* nullable */,
+                                  const uint8_t* d_new /* nullable */, void* stream);
 
 /* Transmit-side counterparts (vector generation for the Monte-Carlo harness, plot_BLER_vs_SNR.m:129):
  * nrldpc_crc_attach_dev replaces crc_calculation + code_block_segmentation of the encoder

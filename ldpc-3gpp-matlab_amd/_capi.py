@@ -114,7 +114,8 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_decode_packed_layers", "nrldpc_pool_set_timing", "nrldpc_pool_last_kernel_ms", "nrldpc_last_host_phases", "nrldpc_payload_bits_dev",
            "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm", "nrldpc_decode_cw", "nrldpc_decode_cw_dev",
            "nrldpc_modulate_dev", "nrldpc_demodulate_dev", "nrldpc_rate_recover_ex_dev", "nrldpc_awgn_dev",
-           "nrldpc_mix_layout", "nrldpc_mix_create", "nrldpc_mix_destroy", "nrldpc_mix_rate_recover_dev", "nrldpc_mix_crc_check_dev"]
+           "nrldpc_mix_layout", "nrldpc_mix_create", "nrldpc_mix_destroy", "nrldpc_mix_rate_recover_dev", "nrldpc_mix_crc_check_dev",
+           "nrldpc_mix_rate_recover_harq_dev", "nrldpc_mix_crc_check_harq_dev"]
 
 _lib = None
 
@@ -197,6 +198,9 @@ def load():
         L.nrldpc_mix_destroy.restype = None
         L.nrldpc_mix_rate_recover_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp]
         L.nrldpc_mix_crc_check_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "nrldpc_mix_rate_recover_harq_dev"):  # the HARQ / CBGTI forms, again without a revision bump
+        L.nrldpc_mix_rate_recover_harq_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp]
+        L.nrldpc_mix_crc_check_harq_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.nrldpc_crc_attach_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_rate_match_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_pool_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), i32, i32, C.POINTER(vp)]
@@ -599,7 +603,10 @@ class MixPlan:
     """nrldpc_mix_*: an immutable plan for a batch whose transport blocks differ in (BG, A, G, Q_m, rv_id, LBRM, C) -- n parameter
     sets (NRLDPC objects or TbParams) with n_tb[i] transport blocks each.  It owns the device-side tables and defines one packed
     layout (.offsets, n + 1 MixOffsets records in elements; entry [n]: the totals) for every array of the receive chain;
-    rate_recover() and crc_check() are one launch each, whatever n.  Streams may share a plan."""
+    rate_recover() and crc_check() are one launch each, whatever n, and so are their HARQ / CBGTI forms rate_recover_harq() and
+    crc_check_harq() (per-transport-block "new HARQ process" flags, per-code-block CBGTI flags, sticky cb_pass, b_hat in/out).
+    rv_id only moves k_0 and no layout field depends on it: a HARQ receiver holds one plan per redundancy version over the same
+    packed arrays.  Streams may share a plan."""
 
     def __init__(self, params, n_tb, device_id=0):
         self._h = C.c_void_p()
@@ -627,6 +634,25 @@ class MixPlan:
     def crc_check(self, d_c_hat, d_b_hat, d_ok, d_cb_pass=None, stream=0):
         """nrldpc_mix_crc_check_dev on raw device addresses of the packed arrays."""
         check(self._lib.nrldpc_mix_crc_check_dev(self._h, _ptr(d_c_hat), _ptr(d_b_hat), _ptr(d_ok), _ptr(d_cb_pass), C.c_void_p(stream)))
+
+    def _harq_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise NRLDPCError("%s has no %s: HARQ / CBGTI state on mixed transport-block batches needs a library built from this "
+                              "tree (NRLDPC_LIB selects an older one?)" % (lib_path(), name))
+        return fn
+
+    def rate_recover_harq(self, d_g_tilde, d_harq, d_cw_llr, d_new=None, in_dtype=LLR_F32, harq_dtype=LLR_F32, out_dtype=LLR_F32, stream=0):
+        """nrldpc_mix_rate_recover_harq_dev on raw device addresses: d_harq is required; d_new (uint8, one per transport block in
+        the packed tb layout; None: no block is new) marks the transport blocks whose buffer rows count as +0.0 and are not read."""
+        check(self._harq_fn("nrldpc_mix_rate_recover_harq_dev")(self._h, _ptr(d_g_tilde), int(in_dtype), _ptr(d_harq), int(harq_dtype),
+                                                                _ptr(d_cw_llr), int(out_dtype), _ptr(d_new), C.c_void_p(stream)))
+
+    def crc_check_harq(self, d_c_hat, d_b_hat, d_ok, d_cb_pass, d_cbgti=None, d_new=None, stream=0):
+        """nrldpc_mix_crc_check_harq_dev on raw device addresses: d_b_hat and d_cb_pass are in/out; d_cbgti (uint8, one per code
+        block in the packed cb layout; None: all 1) and d_new as in rate_recover_harq."""
+        check(self._harq_fn("nrldpc_mix_crc_check_harq_dev")(self._h, _ptr(d_c_hat), _ptr(d_b_hat), _ptr(d_ok), _ptr(d_cb_pass),
+                                                             _ptr(d_cbgti), _ptr(d_new), C.c_void_p(stream)))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

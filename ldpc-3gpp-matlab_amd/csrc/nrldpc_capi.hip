@@ -2140,7 +2140,8 @@ static_assert(nrldpc::MIX_FIELDS * sizeof(int64_t) == sizeof(nrldpc_mix_offsets)
 struct nrldpc_mix {
     int32_t n = 0, device_id = 0;
     std::vector<nrldpc_mix_offsets> off; // n + 1
-    int64_t size_g = 0, size_harq = 0, size_cw = 0, size_c_hat = 0, size_b_hat = 0, size_tb = 0; // elements in use (sum over configurations)
+    int64_t size_g = 0, size_harq = 0, size_cw = 0, size_c_hat = 0, size_cb = 0, size_b_hat = 0, size_tb = 0; // elements in use (sum over configurations)
+    const int64_t* tb_offs = nullptr;    // device, [n]: off[i].tb (the d_new addressing of the HARQ rate recovery)
     char* blob = nullptr;                // every device table, one allocation, written once by nrldpc_mix_create
     nrldpc::MixRmLaunch rm{};
     nrldpc::MixCrcLaunch crc{};
@@ -2264,7 +2265,7 @@ int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb,
     if (!m) return fail(NRLDPC_ERR_NOMEM, "host allocation failed");
     m->n = n; m->device_id = device_id; m->off = mh.off;
     m->size_g = mh.used[nrldpc::MIX_G]; m->size_harq = mh.used[nrldpc::MIX_HARQ]; m->size_cw = mh.used[nrldpc::MIX_CW];
-    m->size_c_hat = mh.used[nrldpc::MIX_C_HAT]; m->size_b_hat = mh.used[nrldpc::MIX_B_HAT]; m->size_tb = mh.used[nrldpc::MIX_TB];
+    m->size_c_hat = mh.used[nrldpc::MIX_C_HAT]; m->size_cb = mh.used[nrldpc::MIX_CB]; m->size_b_hat = mh.used[nrldpc::MIX_B_HAT]; m->size_tb = mh.used[nrldpc::MIX_TB];
     m->rm.n = n; m->rm.n_wg = mh.rm_prefix[n];
     m->crc.n = n; m->crc.n_tb_total = mh.tb_prefix[n];
     m->crc.k_max = mh.k_max; m->crc.c_max = mh.c_max; m->crc.waves = mh.c_max < 4 ? (mh.c_max < 1 ? 1 : mh.c_max) : 4;
@@ -2273,7 +2274,7 @@ int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb,
     auto pad16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_rm = 0, o_crc = o_rm + pad16(mh.rm.size() * sizeof(nrldpc::MixRmRec)), o_rp = o_crc + pad16(mh.crc.size() * sizeof(nrldpc::MixCrcRec)),
                  o_tp = o_rp + pad16(mh.rm_prefix.size() * 4), o_e = o_tp + pad16(mh.tb_prefix.size() * 4), o_o = o_e + pad16(mh.e_tab.size() * 4),
-                 total = o_o + pad16(mh.off_tab.size() * 4);
+                 o_tbo = o_o + pad16(mh.off_tab.size() * 4), total = o_tbo + pad16((size_t)n * 8);
     std::vector<char> img(total, 0);
     memcpy(img.data() + o_rm, mh.rm.data(), mh.rm.size() * sizeof(nrldpc::MixRmRec));
     memcpy(img.data() + o_crc, mh.crc.data(), mh.crc.size() * sizeof(nrldpc::MixCrcRec));
@@ -2281,6 +2282,7 @@ int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb,
     memcpy(img.data() + o_tp, mh.tb_prefix.data(), mh.tb_prefix.size() * 4);
     memcpy(img.data() + o_e, mh.e_tab.data(), mh.e_tab.size() * 4);
     memcpy(img.data() + o_o, mh.off_tab.data(), mh.off_tab.size() * 4);
+    for (int i = 0; i < n; ++i) memcpy(img.data() + o_tbo + (size_t)i * 8, &mh.off[i].tb, 8);
     DeviceScope scope(device_id);
     hipError_t e = scope.err;
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->blob), total);
@@ -2292,6 +2294,7 @@ int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb,
     m->crc.prefix = reinterpret_cast<const int32_t*>(m->blob + o_tp);
     m->rm.e_tab = reinterpret_cast<const int32_t*>(m->blob + o_e);
     m->rm.off_tab = reinterpret_cast<const int32_t*>(m->blob + o_o);
+    m->tb_offs = reinterpret_cast<const int64_t*>(m->blob + o_tbo);
     *out = m;
     return NRLDPC_OK;
     NRLDPC_API_END
@@ -2325,6 +2328,46 @@ int nrldpc_mix_crc_check_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, uint8_
     DeviceScope scope(m->device_id);
     if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
     hipError_t e = nrldpc::launch_mix_crc_check(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix CRC kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_rate_recover_harq_dev(nrldpc_mix_handle m, const void* d_g_tilde, int32_t in_dtype, void* d_harq, int32_t harq_dtype,
+                                     void* d_cw_llr, int32_t out_dtype, const uint8_t* d_new, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    auto known = [](int32_t d) { return d == NRLDPC_LLR_F32 || d == NRLDPC_LLR_F16; };
+    if (!known(in_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "in_dtype must be f32 or f16");
+    if (!known(harq_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "harq_dtype must be f32 or f16");
+    if (!known(out_dtype)) return fail(NRLDPC_ERR_UNSUPPORTED, "out_dtype must be f32 or f16");
+    if ((m->size_cw > 0 && !d_cw_llr) || (m->size_g > 0 && !d_g_tilde) || (m->size_harq > 0 && !d_harq)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->rm.n_wg == 0) return NRLDPC_OK;
+    nrldpc::MixRmHarqLaunch a;
+    a.b = m->rm;
+    a.b.g = d_g_tilde; a.b.harq = d_harq; a.b.out = d_cw_llr;
+    a.b.in_f16 = in_dtype == NRLDPC_LLR_F16; a.b.harq_f16 = harq_dtype == NRLDPC_LLR_F16; a.b.out_f16 = out_dtype == NRLDPC_LLR_F16;
+    a.tb_offs = m->tb_offs; a.is_new = d_new;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    // no flags: every transport block continues -- that IS nrldpc_mix_rate_recover_dev, and its kernel is launched
+    hipError_t e = d_new ? nrldpc::launch_mix_rate_recover_harq(a, static_cast<hipStream_t>(stream))
+                         : nrldpc::launch_mix_rate_recover(a.b, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix rate-recovery kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_crc_check_harq_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, uint8_t* d_b_hat, int32_t* d_ok, int32_t* d_cb_pass,
+                                  const uint8_t* d_cbgti, const uint8_t* d_new, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if ((m->size_c_hat > 0 && !d_c_hat) || (m->size_b_hat > 0 && !d_b_hat) || (m->size_tb > 0 && !d_ok)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->size_cb > 0 && !d_cb_pass) return fail(NRLDPC_ERR_ARG, "the sticky code-block flags (d_cb_pass) are required");
+    if (m->crc.n_tb_total == 0) return NRLDPC_OK;
+    nrldpc::MixCrcHarqLaunch a;
+    a.b = m->crc;
+    a.b.c_hat = d_c_hat; a.b.b_hat = d_b_hat; a.b.ok = d_ok; a.b.cb_pass = d_cb_pass;
+    a.cbgti = d_cbgti; a.is_new = d_new;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_crc_check_harq(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hipfail(e, "mix CRC kernel launch");
     return NRLDPC_OK;
 }

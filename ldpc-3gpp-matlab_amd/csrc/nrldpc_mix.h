@@ -1,5 +1,6 @@
 // nrldpc_mix.h -- mixed transport-block batches: the packed layout, the device-side tables and the workgroup mapping of
-// nrldpc_mix_rate_recover_dev / nrldpc_mix_crc_check_dev (nrldpc_mix.hip; semantics: include/nrldpc.h).
+// nrldpc_mix_rate_recover_dev / nrldpc_mix_crc_check_dev and their HARQ forms nrldpc_mix_rate_recover_harq_dev /
+// nrldpc_mix_crc_check_harq_dev (nrldpc_mix.hip; semantics: include/nrldpc.h, DESIGN.md sections 4.15 and 4.16).
 // (Not in nrldpc_kernels.h: that header is part of the decoder kernels' identity, nrldpc_kernel_id.)
 //
 // The first part -- layout arithmetic, table records, the workgroup -> (configuration, code block, tile) mapping -- is plain C++
@@ -81,6 +82,17 @@ NRLDPC_MIX_HD MixRmWork mix_rm_work(const int32_t* prefix, const MixRmRec* recs,
 
 NRLDPC_MIX_HD int32_t mix_rm_wg_per_cb(int32_t ncwz) { return (ncwz + MIX_RM_WG - 1) / MIX_RM_WG; }
 
+// ---- the flag arrays of the HARQ forms (tests/mix_host/mix_harq_check.cpp walks these on the CPU too) ----------------------------------
+// d_new: one byte per transport block in the packed `tb` layout; d_cbgti: one byte per code block in the packed `cb` layout.
+// tb_off / cb_off: where the configuration's segment starts in that layout (nrldpc_mix_offsets::tb / ::cb).
+NRLDPC_MIX_HD int64_t mix_new_index(int64_t tb_off, int32_t tb) { return tb_off + tb; }
+NRLDPC_MIX_HD int64_t mix_cbgti_index(int64_t cb_off, int32_t C, int32_t tb, int32_t r) { return cb_off + (int64_t)tb * C + r; }
+// the d_new element of a rate-recovery workgroup (a workgroup is one code block of ONE transport block: the flag is workgroup-uniform);
+// tb_offs[i] = nrldpc_mix_offsets::tb of configuration i
+NRLDPC_MIX_HD int64_t mix_rm_new_index(const int64_t* tb_offs, const MixRmRec* recs, const MixRmWork& w) {
+    return mix_new_index(tb_offs[w.cfg], w.blk / recs[w.cfg].C);
+}
+
 } // namespace nrldpc
 
 #if defined(__HIPCC__)
@@ -111,6 +123,15 @@ struct MixRmLaunch {
 };
 hipError_t launch_mix_rate_recover(const MixRmLaunch& a, hipStream_t stream);
 
+// The HARQ form: the same launch block plus the per-transport-block "starts a new HARQ process" flags.  A structure of its own, so
+// that the argument block -- and with it the code -- of the plain kernels stays what it was.
+struct MixRmHarqLaunch {
+    MixRmLaunch b;            // b.harq is never null here
+    const int64_t* tb_offs;   // device, [n]: nrldpc_mix_offsets::tb of every configuration
+    const uint8_t* is_new;    // device, packed tb layout; never null (no flags: the plain kernel is launched)
+};
+hipError_t launch_mix_rate_recover_harq(const MixRmHarqLaunch& a, hipStream_t stream);
+
 struct MixCrcLaunch {
     const MixCrcRec* recs;    // device, [n]
     const int32_t* prefix;    // device, [n + 1] transport blocks
@@ -123,6 +144,14 @@ struct MixCrcLaunch {
     int32_t* cb_pass;         // nullable
 };
 hipError_t launch_mix_crc_check(const MixCrcLaunch& a, hipStream_t stream);
+
+// The HARQ form (the state machine of nrldpc_crc_check_kernel per transport block): b.cb_pass is in/out and never null
+struct MixCrcHarqLaunch {
+    MixCrcLaunch b;
+    const uint8_t* cbgti;     // device, packed cb layout; null = every flag 1
+    const uint8_t* is_new;    // device, packed tb layout; null = no transport block starts a new HARQ process
+};
+hipError_t launch_mix_crc_check_harq(const MixCrcHarqLaunch& a, hipStream_t stream);
 
 } // namespace nrldpc
 #endif

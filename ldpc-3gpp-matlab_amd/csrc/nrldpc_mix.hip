@@ -1,5 +1,9 @@
 // nrldpc_mix.hip -- rate recovery and the CRC stage for a MIX of transport-block configurations in one launch each
-// (nrldpc_mix_rate_recover_dev, nrldpc_mix_crc_check_dev; semantics: include/nrldpc.h).
+// (nrldpc_mix_rate_recover_dev, nrldpc_mix_crc_check_dev; semantics: include/nrldpc.h), and their HARQ forms
+// (nrldpc_mix_rate_recover_harq_dev, nrldpc_mix_crc_check_harq_dev): the same two kernels instantiated with
+// HARQ = true, which adds a per-transport-block "starts a new HARQ process" flag to both and the sticky code-block flags, CBGTI and
+// the kept b_hat segments of nrldpc_crc_check_kernel to the CRC stage.  The HARQ = false instantiations compile to the code they
+// were before the parameter existed (every addition sits under if constexpr, the argument block is a structure of its own).
 //
 // Both kernels are table driven.  The per-configuration records (scalar parameters, E_r and its offsets, the two CRC plans) and a
 // prefix table over the work items live in device memory, uploaded once by nrldpc_mix_create and never written again; a
@@ -70,10 +74,33 @@ template <typename HbT> __device__ __forceinline__ float combine(float sum, HbT&
 // The tail for the four positions pos0 .. pos0+3 of a code block's decoder input (p0 = pos0 - 2Z in d): val[t] = what this
 // transmission delivers, fill[t] = filler (+inf), inb[t] = a non-filler position of the circular buffer, keep[t] = the position
 // receives nothing and the configuration leaves such buffer entries as they are (MixRmRec::echo): read, not written.
-template <typename HbT, typename OutT>
+// HARQ && fresh (workgroup-uniform): the transport block starts a new HARQ process -- the buffer counts as +0.0 and is NOT read; every
+// non-filler position inside the circular buffer takes narrow(sum + 0), the kept ones included (they would echo the +0).
+template <bool HARQ, typename HbT, typename OutT>
 __device__ __forceinline__ void finish4(HbT* hb, OutT* out, int pos0, int p0, int ncwz, float (&val)[4], const bool (&fill)[4], const bool (&inb)[4],
-                                        const bool (&keep)[4]) {
-    if (hb) {
+                                        const bool (&keep)[4], bool fresh) {
+    bool done = false;
+    if constexpr (HARQ) {
+        if (fresh) {
+            float zero = 0.0f;
+            asm volatile("" : "+v"(zero)); // opaque to the optimiser: sum + 0 stays an add whatever the flags, and -0 becomes +0
+            HbT h[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                h[t] = narrow<HbT>(val[t] + zero);
+                if (inb[t]) val[t] = (float)h[t];
+            }
+            if (inb[0] && inb[1] && inb[2] && inb[3]) {
+                store4(hb + p0, h);
+            } else {
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    if (inb[t]) hb[p0 + t] = h[t];
+            }
+            done = true;
+        }
+    }
+    if (hb && !done) {
         if (inb[0] && inb[1] && inb[2] && inb[3] && !(keep[0] || keep[1] || keep[2] || keep[3])) {
             HbT h[4];
             load4(hb + p0, h);
@@ -109,8 +136,14 @@ __device__ __forceinline__ void finish4(HbT* hb, OutT* out, int pos0, int p0, in
 } // namespace
 
 // ---- rate recovery ---------------------------------------------------------------------------------------------------------------
-template <typename InT, typename HbT, typename OutT>
-__global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const MixRmLaunch a) {
+template <bool HARQ> struct MixRmArgs { typedef MixRmLaunch type; };
+template <> struct MixRmArgs<true> { typedef MixRmHarqLaunch type; };
+__device__ __forceinline__ const MixRmLaunch& base_of(const MixRmLaunch& a) { return a; }
+__device__ __forceinline__ const MixRmLaunch& base_of(const MixRmHarqLaunch& a) { return a.b; }
+
+template <typename InT, typename HbT, typename OutT, bool HARQ>
+__global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const typename MixRmArgs<HARQ>::type args) {
+    const MixRmLaunch& a = base_of(args);
     const MixRmWork w = mix_rm_work(a.prefix, a.recs, a.n, (int)blockIdx.x);
     const MixRmRec& c = a.recs[w.cfg];
     const int blk = w.blk; // tb * C + r
@@ -132,6 +165,8 @@ __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const MixR
     HbT* hb = a.harq ? static_cast<HbT*>(a.harq) + c.harq_off + (int64_t)blk * N_cb : nullptr;
     OutT* out = static_cast<OutT*>(a.out) + c.cw_off + (int64_t)blk * ncwz;
     const bool echo = hb && c.echo;
+    bool fresh = false; // workgroup-uniform: a workgroup is one code block of one transport block
+    if constexpr (HARQ) fresh = args.is_new[mix_rm_new_index(args.tb_offs, a.recs, w)] != 0;
     if (c.form == 0) {
         // the general gather: repetitions summed in ascending k (:229-231), then the buffer
         const int Pq = P / rows, Pr = P - Pq * rows; // a repetition is P positions of e further on
@@ -172,7 +207,7 @@ __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const MixR
                     if (q == P) { q = 0; j = 0; i = 0; }
                 }
             }
-            finish4(hb, out, pos0, pos0 - 2 * Z, ncwz, val, fill, inb, keep);
+            finish4<HARQ>(hb, out, pos0, pos0 - 2 * Z, ncwz, val, fill, inb, keep, fresh);
         }
         return;
     }
@@ -204,7 +239,7 @@ __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const MixR
         // f already points one past the transport block's LLRs
 #pragma unroll
         for (int t = 0; t < 4; ++t) val[t] = live[t] ? (float)f[idx[t]] : 0.0f;
-        finish4(hb, out, pos0, pos0 - 2 * Z, ncwz, val, fill, inb, keep);
+        finish4<HARQ>(hb, out, pos0, pos0 - 2 * Z, ncwz, val, fill, inb, keep, fresh);
     }
 }
 
@@ -214,14 +249,33 @@ hipError_t launch_mix_rate_recover(const MixRmLaunch& a, hipStream_t stream) {
     auto with_out = [&](auto in, auto hb) {
         typedef decltype(in) InT;
         typedef decltype(hb) HbT;
-        if (a.out_f16) hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, half_t>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, float>), grid, block, 0, stream, a);
+        if (a.out_f16) hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, half_t, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, float, false>), grid, block, 0, stream, a);
     };
     auto with_hb = [&](auto in) {
         if (a.harq && a.harq_f16) with_out(in, half_t{});
         else with_out(in, float{}); // (without a buffer its type is never used)
     };
     if (a.in_f16) with_hb(half_t{});
+    else with_hb(float{});
+    return hipGetLastError();
+}
+
+hipError_t launch_mix_rate_recover_harq(const MixRmHarqLaunch& a, hipStream_t stream) {
+    if (a.b.n_wg <= 0) return hipSuccess;
+    if (!a.b.harq || !a.is_new || !a.tb_offs) return hipErrorInvalidValue; // (the C ABI never gets here: it launches the plain kernel)
+    const dim3 grid(a.b.n_wg), block(256);
+    auto with_out = [&](auto in, auto hb) {
+        typedef decltype(in) InT;
+        typedef decltype(hb) HbT;
+        if (a.b.out_f16) hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, half_t, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, float, true>), grid, block, 0, stream, a);
+    };
+    auto with_hb = [&](auto in) {
+        if (a.b.harq_f16) with_out(in, half_t{});
+        else with_out(in, float{});
+    };
+    if (a.b.in_f16) with_hb(half_t{});
     else with_hb(float{});
     return hipGetLastError();
 }
@@ -267,8 +321,17 @@ __host__ __device__ __forceinline__ int mix_row_capacity(int K) { return ((K + 1
 
 } // namespace
 
-// one workgroup per transport block, one wave per code block (waves loop when C exceeds the workgroup's waves)
-__global__ __launch_bounds__(256) void nrldpc_mix_crc_check_kernel(const MixCrcLaunch a) {
+template <bool HARQ> struct MixCrcArgs { typedef MixCrcLaunch type; };
+template <> struct MixCrcArgs<true> { typedef MixCrcHarqLaunch type; };
+__device__ __forceinline__ const MixCrcLaunch& base_of(const MixCrcLaunch& a) { return a; }
+__device__ __forceinline__ const MixCrcLaunch& base_of(const MixCrcHarqLaunch& a) { return a.b; }
+
+// one workgroup per transport block, one wave per code block (waves loop when C exceeds the workgroup's waves).
+// HARQ: the state machine of nrldpc_crc_check_kernel (NRLDPCDecoder.m:286-316, 337) with keep_b_hat = sticky = !new[tb] and the CBGTI
+// flag read per code block -- a transport block that starts a new HARQ process is reset() followed by a step, for that block alone.
+template <bool HARQ>
+__global__ __launch_bounds__(256) void nrldpc_mix_crc_check_kernel(const typename MixCrcArgs<HARQ>::type args) {
+    const MixCrcLaunch& a = base_of(args);
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6, lane = threadIdx.x & 63;
     const int cfg = mix_find(a.prefix, a.n, (int)blockIdx.x);
@@ -282,16 +345,26 @@ __global__ __launch_bounds__(256) void nrldpc_mix_crc_check_kernel(const MixCrcL
     const uint8_t* chat = a.c_hat + c.c_hat_off + (int64_t)tb * C * K;
     uint8_t* b_hat = a.b_hat + c.b_hat_off + (int64_t)tb * c.B;
     const int pay = Kp - c.Lcb; // payload bits per code block
+    bool keep = false; // workgroup-uniform: the transport block continues a HARQ process (b_hat and cb_pass are in/out)
+    if constexpr (HARQ) keep = !(args.is_new && args.is_new[mix_new_index(c.tb_off, tb)] != 0);
     for (int r = wave; r < C; r += nw) {
         wave_lds_sync(); // previous round's readers are done with the row
         const uint8_t* row = stage_row(base, chat + (size_t)r * K, Kp);
         wave_lds_sync();
         int fail = 0;
         if (C > 1) fail = wave_crc(row, Kp, c.cb) != 0; // NRLDPCDecoder.m:298-301
+        if constexpr (HARQ) {                            // :304: CRC holds AND the block was (re)transmitted
+            if (args.cbgti) fail |= args.cbgti[mix_cbgti_index(c.cb_off, C, tb, r)] == 0;
+        }
         uint32_t p;
         if (!fail) {
             p = wave_crc(row, pay, c.tb);
             store_row(b_hat + (size_t)r * pay, row, pay); // :303-309 payload copy
+        } else if (HARQ && keep) {                        // :286-287: the segment keeps what an earlier step stored
+            wave_lds_sync();
+            row = stage_row(base, b_hat + (size_t)r * pay, pay);
+            wave_lds_sync();
+            p = wave_crc(row, pay, c.tb);
         } else {                                          // :289: b_hat = zeros(B,1)
             p = 0;
             uint8_t* z = b_hat + (size_t)r * pay;
@@ -305,8 +378,14 @@ __global__ __launch_bounds__(256) void nrldpc_mix_crc_check_kernel(const MixCrcL
         for (int r = 0; r < C; ++r) reg = gf2_apply(c.tb.horner, reg) ^ part[r];
         int any_cb = 0;   // :337 any(~code_block_CRC_passed)
         for (int r = lane; r < C; r += 64) {
-            const int pass = cb_fail[r] ? 0 : 1;
-            if (a.cb_pass) a.cb_pass[c.cb_off + (int64_t)tb * C + r] = pass;
+            int pass = cb_fail[r] ? 0 : 1;
+            if constexpr (HARQ) {                         // flags sticky (:305, 315) unless the block starts anew (:355)
+                int32_t* f = a.cb_pass + c.cb_off + (int64_t)tb * C + r;
+                if (keep) pass |= (*f != 0);
+                *f = pass;
+            } else {
+                if (a.cb_pass) a.cb_pass[c.cb_off + (int64_t)tb * C + r] = pass;
+            }
             any_cb |= !pass;
         }
         any_cb = __any(any_cb);
@@ -317,7 +396,15 @@ __global__ __launch_bounds__(256) void nrldpc_mix_crc_check_kernel(const MixCrcL
 hipError_t launch_mix_crc_check(const MixCrcLaunch& a, hipStream_t stream) {
     if (a.n_tb_total <= 0) return hipSuccess;
     const size_t lds = (size_t)a.waves * mix_row_capacity(a.k_max) + 8 * (size_t)a.c_max + 16;
-    hipLaunchKernelGGL(nrldpc_mix_crc_check_kernel, dim3(a.n_tb_total), dim3(64 * a.waves), lds, stream, a);
+    hipLaunchKernelGGL(nrldpc_mix_crc_check_kernel<false>, dim3(a.n_tb_total), dim3(64 * a.waves), lds, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mix_crc_check_harq(const MixCrcHarqLaunch& a, hipStream_t stream) {
+    if (a.b.n_tb_total <= 0) return hipSuccess;
+    if (!a.b.cb_pass) return hipErrorInvalidValue; // (refused by the C ABI before it gets here)
+    const size_t lds = (size_t)a.b.waves * mix_row_capacity(a.b.k_max) + 8 * (size_t)a.b.c_max + 16;
+    hipLaunchKernelGGL(nrldpc_mix_crc_check_kernel<true>, dim3(a.b.n_tb_total), dim3(64 * a.b.waves), lds, stream, a);
     return hipGetLastError();
 }
 

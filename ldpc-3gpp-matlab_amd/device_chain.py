@@ -4,6 +4,8 @@
 per transport block (NRLDPCDecoder.m:133-140); here one transport-block batch is three kernel launches
 with no host loop and no PCIe traffic in between.  torch is used for device memory only.
 """
+import copy
+
 import numpy as np
 
 from ._capi import LLR_F16, LLR_F32, MIX_FIELDS, Codec, MixPlan, MultiCall, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
@@ -156,15 +158,28 @@ class MixedDecodeChain:
     decoder (nrldpc_decode_multi_dev: a handful), the mix CRC stage (one launch).  Every array is PACKED: configuration i's segment
     starts at plan.offsets[i].<field> elements and is exactly the array DeviceDecodeChain uses for that configuration;
     views() / pack() convert.  One codec per configuration (its layer count from active_layers() when prune_layers) and one
-    MultiCall, both built once.  The chain keeps no HARQ state (I_HARQ = 0, no CBGTI state machine); a soft buffer is reachable at
-    the MixPlan level (plan.rate_recover with d_harq)."""
+    MultiCall, both built once.
+
+    I_HARQ = 0 (the default): no state, every step stands alone.  I_HARQ != 0: the chain owns the DiscreteState of the reference's
+    decoder (NRLDPCDecoder.m:64-95) for every transport block of the mix, packed and zero-initialised -- `harq` (d_tilde_buffer, f32
+    or f16 by harq_dtype), `cb_pass` (the sticky code_block_CRC_passed), `cbgti` (CBGTI_flags of each parameter object, filled once)
+    and `b_hat`, which becomes in/out (b_hat_buffer) -- and step() takes the redundancy version(s) and a per-transport-block "starts
+    a new HARQ process" flag array; reset() clears the state of every block (:343-356), a flag that of one block.  A plan is immutable
+    and rv_id only moves k_0, so the chain holds one MixPlan per distinct tuple of redundancy versions over the same arrays."""
 
     _SHAPES = {"g": lambda t, n: (n, t.G), "harq": lambda t, n: (n, t.C, t.N_cb), "cw": lambda t, n: (n * t.C, 2 * t.Z + t.N),
                "c_hat": lambda t, n: (n * t.C, t.K), "cb": lambda t, n: (n, t.C), "b_hat": lambda t, n: (n, t.B), "tb": lambda t, n: (n,)}
 
     def __init__(self, params, n_tb, iterations=50, alpha=None, beta=0.0, llr_scale=0, prune_layers=True, llr_dtype=None,
-                 algorithm="min-sum", device_id=0):
+                 algorithm="min-sum", device_id=0, I_HARQ=0, harq_dtype=None):
         algorithm_code(algorithm)  # UnsupportedParameters for an unknown name, before any device work
+        try:
+            self.harq_dtype = np.dtype(np.float32 if harq_dtype is None else harq_dtype)
+        except TypeError:
+            self.harq_dtype = None
+        if self.harq_dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+            raise UnsupportedParameters("harq_dtype should be numpy float32 or float16, not %r." % (harq_dtype,))
+        self.I_HARQ = int(I_HARQ)
         import torch
         self.torch = torch
         params = list(params)
@@ -177,8 +192,13 @@ class MixedDecodeChain:
             raise UnsupportedParameters("llr_dtype should be numpy float32 or float16, not %r." % (llr_dtype,))
         self.dev = torch.device("cuda", device_id)
         self.device_id = device_id
+        self.prune = bool(prune_layers)
         self.plan = MixPlan(params, self.n_tb, device_id=device_id)
+        self._own_rv = tuple(int(p.rv_id) for p in params)
+        self._plans = {self._own_rv: self.plan}  # one plan per tuple of redundancy versions (only I_HARQ steps add to it)
+        self._acts = {self._own_rv: [p.active_layers() for p in params]}
         self.codecs = []
+        self.harq = self.cb_pass = self.cbgti = None
         try:
             for p in params:
                 rows = 46 if p.BG == 1 else 42
@@ -194,6 +214,16 @@ class MixedDecodeChain:
             self.b_hat = torch.zeros(tot.b_hat, dtype=torch.uint8, device=self.dev)
             self.ok = torch.zeros(tot.tb, dtype=torch.int32, device=self.dev)
             n = len(params)
+            # what each codec runs at now, and (I_HARQ, prune_layers) the sticky maximum over the redundancy versions since reset()
+            self._codec_layers = [p.active_layers() if prune_layers else (46 if p.BG == 1 else 42) for p in params]
+            self._layers_seen = [4] * n
+            if self.I_HARQ:
+                self.harq = torch.zeros(tot.harq, dtype=torch.float16 if self.harq_dtype == np.float16 else torch.float32, device=self.dev)
+                self.cb_pass = torch.zeros(tot.cb, dtype=torch.int32, device=self.dev)
+                self.cbgti = torch.ones(tot.cb, dtype=torch.uint8, device=self.dev)
+                for v, p, k in zip(self.views(self.cbgti, "cb"), params, self.n_tb):
+                    if k:
+                        v.copy_(torch.tensor([1 if f else 0 for f in p.CBGTI_flags], dtype=torch.uint8).repeat(k, 1))
             self._multi = MultiCall(self.codecs, [self.cw_llr.data_ptr() + off[i].cw * self.llr_dtype.itemsize for i in range(n)],
                                     [self.n_tb[i] * params[i].C for i in range(n)], [self.c_hat.data_ptr() + off[i].c_hat for i in range(n)],
                                     [self.iters.data_ptr() + 4 * off[i].cb for i in range(n)]) if n else None
@@ -206,8 +236,45 @@ class MixedDecodeChain:
             c.close()
         self.codecs = []
         self._multi = None
+        for plan in getattr(self, "_plans", {}).values():
+            plan.close()
+        self._plans = {}
         if getattr(self, "plan", None) is not None:
             self.plan.close()
+
+    def reset(self):
+        """reset(hDec) for every transport block of the mix: clears d_tilde_buffer, b_hat_buffer and code_block_CRC_passed
+        (NRLDPCDecoder.m:343-356), and the sticky layer counts."""
+        for t in (self.harq, self.b_hat, self.cb_pass):
+            if t is not None:
+                t.zero_()
+        self._layers_seen = [4] * len(self.params)
+
+    def _plan_for(self, rv_id):
+        """The plan (and the active layer counts) for a step's redundancy versions: None = the parameter objects' own, one int for
+        every configuration, or a sequence of n.  Built on first use from copies of the parameter objects, then cached."""
+        n = len(self.params)
+        if rv_id is None:
+            key = self._own_rv
+        elif isinstance(rv_id, (int, np.integer)):
+            key = (int(rv_id),) * n
+        else:
+            key = tuple(int(x) for x in rv_id)
+            if len(key) != n:
+                raise NRLDPCError("rv_id should be None, one value or one value per configuration (%d), got %d." % (n, len(key)))
+        if key not in self._plans:
+            ps = []
+            for p, rv in zip(self.params, key):
+                q = copy.copy(p)
+                q.rv_id = rv  # (UnsupportedParameters for a value outside 0 ... 3)
+                ps.append(q)
+            plan = MixPlan(ps, self.n_tb, device_id=self.device_id)
+            same = all(getattr(a, f) == getattr(b, f) for a, b in zip(plan.offsets, self.plan.offsets) for f in MIX_FIELDS)
+            if not same or len(plan.offsets) != len(self.plan.offsets):
+                plan.close()
+                raise NRLDPCError("the layout of the plan for rv_id %r differs from the chain's: its packed arrays cannot be shared." % (key,))
+            self._plans[key], self._acts[key] = plan, [q.active_layers() for q in ps]
+        return self._plans[key], self._acts[key]
 
     def views(self, packed, field):
         """The per-configuration views of a packed tensor: field is one of "g", "harq", "cw", "c_hat", "cb" (iters, cb_pass), "b_hat",
@@ -238,8 +305,12 @@ class MixedDecodeChain:
             v.copy_(x)
         return packed
 
-    def step(self, g_tilde_packed):
+    def step(self, g_tilde_packed, rv_id=None, new=None):
         """g_tilde_packed: the packed float32 or float16 demodulator LLRs on the device (plan.totals.g elements; pack(..., "g")).
+        With I_HARQ != 0 only: rv_id = the redundancy version(s) of this transmission (None: the parameter objects' own; one int for
+        all configurations; a sequence of n), new = None or a packed uint8 device tensor of plan.totals.tb elements (pack(..., "tb")),
+        non-zero where a transport block starts a new HARQ process in this step: its soft-buffer rows count as zero and are not read,
+        its code-block flags and b_hat segments start from nothing -- reset() followed by a step, for that block alone.
         Returns (b_hat_packed uint8, ok int32, iters int32): the chain's own packed device arrays, valid until the next step (clone
         what must live longer); views(b_hat_packed, "b_hat")[i][:, :A] is a_hat of configuration i, views(ok, "tb")[i] its flags
         (0 where the reference returns []), views(iters, "cb")[i] its iteration counts [n_tb][C]."""
@@ -249,6 +320,11 @@ class MixedDecodeChain:
             raise NRLDPCError("g_tilde should be a contiguous 1-D float32 or float16 device tensor of at least %d elements." % self.plan.totals.g)
         if g.device != self.dev:
             raise NRLDPCError("g_tilde lives on %s, this chain on %s." % (g.device, self.dev))
+        if not self.I_HARQ:
+            if rv_id is not None or new is not None:
+                raise NRLDPCError("rv_id and new belong to a chain with HARQ state (I_HARQ ~= 0).")
+        else:
+            return self._step_harq(g, rv_id, new)
         with torch.cuda.device(self.dev):
             stream = torch.cuda.current_stream(self.dev).cuda_stream
             self.plan.rate_recover(g.data_ptr() if g.numel() else None, None, self.cw_llr.data_ptr(), in_dtype=LLR_F16 if g.dtype == torch.float16 else LLR_F32,
@@ -256,6 +332,35 @@ class MixedDecodeChain:
             if self._multi is not None:
                 self._multi(stream)
             self.plan.crc_check(self.c_hat.data_ptr(), self.b_hat.data_ptr(), self.ok.data_ptr(), None, stream=stream)
+        return self.b_hat, self.ok, self.iters
+
+    def _step_harq(self, g, rv_id, new):
+        torch = self.torch
+        if new is not None:
+            if (new.dim() != 1 or new.dtype != torch.uint8 or not new.is_cuda or not new.is_contiguous() or new.numel() < self.plan.totals.tb
+                    or new.device != self.dev):
+                raise NRLDPCError("new should be a contiguous 1-D uint8 tensor of at least %d elements on %s." % (self.plan.totals.tb, self.dev))
+        plan, acts = self._plan_for(rv_id)
+        if self.prune:
+            # a row that carried an LLR in an earlier redundancy version still does (the buffer holds it): the sticky maximum.
+            # More rows than a block needs are exact, only slower (a flagged block does not lower its configuration's count).
+            for i, codec in enumerate(self.codecs):
+                self._layers_seen[i] = max(self._layers_seen[i], acts[i])
+                if self._codec_layers[i] != self._layers_seen[i]:
+                    codec.set_layers(self._layers_seen[i])
+                    self._codec_layers[i] = self._layers_seen[i]
+        f16 = torch.float16
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            d_new = new.data_ptr() if new is not None and new.numel() else None
+            plan.rate_recover_harq(g.data_ptr() if g.numel() else None, self.harq.data_ptr() if self.harq.numel() else None,
+                                   self.cw_llr.data_ptr(), d_new, in_dtype=LLR_F16 if g.dtype == f16 else LLR_F32,
+                                   harq_dtype=LLR_F16 if self.harq_dtype == np.float16 else LLR_F32,
+                                   out_dtype=LLR_F16 if self.llr_dtype == np.float16 else LLR_F32, stream=stream)
+            if self._multi is not None:
+                self._multi(stream)
+            plan.crc_check_harq(self.c_hat.data_ptr(), self.b_hat.data_ptr(), self.ok.data_ptr(), self.cb_pass.data_ptr(),
+                                self.cbgti.data_ptr(), d_new, stream=stream)
         return self.b_hat, self.ok, self.iters
 
 
