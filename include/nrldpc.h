@@ -295,7 +295,8 @@ int nrldpc_pool_last_split(nrldpc_pool_handle p, int32_t* counts);
 void nrldpc_pool_destroy(nrldpc_pool_handle p);
 
 /* Systematic encode.  info: [batch][K] bytes {0,1}; cw: [batch][ncols*Z] bytes {0,1} = [info;parity]
- * with H*cw = 0 (NRLDPCEncoder.m:158). */
+ * with H*cw = 0 (NRLDPCEncoder.m:158).  Only bit 0 of an input byte is read: a byte b encodes as b & 1, and
+ * every output byte, the systematic copy included, is 0 or 1.  Neither pointer needs any alignment. */
 int nrldpc_encode(nrldpc_handle h, const uint8_t* info, int32_t batch, uint8_t* cw);
 int nrldpc_encode_dev(nrldpc_handle h, const uint8_t* d_info, int32_t batch, uint8_t* d_cw, void* stream);
 
