@@ -38,6 +38,7 @@
 #include "nrldpc_modem.h"
 #include "nrldpc_ratematch_ex.h"
 #include "nrldpc_mix.h"
+#include "nrldpc_rm_core.h"
 
 static_assert(sizeof(nrldpc_cw_out) == 32, "nrldpc_cw_out: the size include/nrldpc.h states");
 
@@ -2204,14 +2205,11 @@ int mix_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool ta
         r.g_off = cur[nrldpc::MIX_G]; r.harq_off = cur[nrldpc::MIX_HARQ]; r.cw_off = cur[nrldpc::MIX_CW];
         r.n_tb = n_tb[i]; r.C = q->C; r.G = q->G; r.Z = q->Z; r.K = q->K; r.Kp = q->K_prime; r.N = q->N; r.N_cb = q->N_cb;
         r.k0 = q->k_0; r.Qm = q->Q_m;
-        // the launch rule of launch_rate_recover_ex (nrldpc_ratematch_ex.hip), without its environment knobs
-        const int lo_f = q->K_prime - 2 * q->Z > 0 ? q->K_prime - 2 * q->Z : 0, hi_f = q->K - 2 * q->Z;
-        const int f_hi = hi_f < q->N_cb ? hi_f : q->N_cb;
-        const int P = q->N_cb - (f_hi > lo_f ? f_hi - lo_f : 0);
-        bool repeats = !(q->Q_m == 1 || q->Q_m == 2 || q->Q_m == 4 || q->Q_m == 6 || q->Q_m == 8);
-        for (int b = 0; b < q->C; ++b) repeats = repeats || q->E_r[b] > P;
-        r.form = repeats ? 0 : 1;
-        r.echo = (!repeats && q->Q_m <= 2 && q->N >= 4096) ? 1 : 0;
+        // the launch rule of the single-configuration calls without its environment knobs; the mix has no input-driven form
+        // (asked without a buffer the rule answers general or plain gather) and takes `echo` in its place
+        const nrldpc::RmRule rule = nrldpc::rm_launch_rule(nrldpc::RmGeom(q->Z, q->K, q->K_prime, q->N_cb, q->k_0), q->E_r, q->C, q->Q_m, q->N, false);
+        r.form = rule.form;
+        r.echo = rule.echo;
         r.e_base = (int32_t)m.e_tab.size();
         r.wg_per_cb = per;
         for (int b = 0; b < q->C; ++b) { m.e_tab.push_back(blocks.E[b]); m.off_tab.push_back(blocks.off[b]); }

@@ -12,134 +12,30 @@
 // depend on the number of configurations: one per stage.
 //
 // Rate recovery is the gather of nrldpc_ratematch_ex.hip -- four neighbouring positions of a code block's decoder input per lane,
-// the same index arithmetic, the same f32 sums in the same order (repetitions in ascending k, then the buffer), the same clamp
-// before any conversion to f16 -- and leaves bit for bit what nrldpc_rate_recover_ex_dev leaves in every segment.  A segment of
+// through the same gather bodies, element rules and tail (nrldpc_rm_core.h: repetitions in ascending k, then the buffer, the clamp
+// before any conversion to f16) -- and leaves bit for bit what nrldpc_rate_recover_ex_dev leaves in every segment.  A segment of
 // a packed array starts 16 elements aligned, its rows do not (odd G, odd N_cb): every access wider than one element is taken by
 // a test on the address it would use.  Every buffer position is read and written by exactly one thread; no atomics.
 //
-// The CRC stage is the wave-per-code-block kernel of nrldpc_crc.hip (LDS staging, per-lane bit-serial register, GF(2) combine
-// tree, Horner fold of the segment remainders for the transport-block CRC) with the plans read from the record.
+// The CRC stage is the wave-per-code-block kernel of nrldpc_crc.hip (LDS staging, then the per-lane bit-serial register, the GF(2)
+// combine tree and the Horner fold of the segment remainders of nrldpc_crc_wave.h) with the plans read from the record.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
+#include "nrldpc_crc_wave.h"
 #include "nrldpc_mix.h"
+#include "nrldpc_rm_core.h"
 #include "nrldpc_wave.h"
 
 namespace nrldpc {
-namespace {
-
-typedef _Float16 half_t;
-
-// ---- element helpers: the rules of nrldpc_ratematch_ex.hip ---------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ T narrow(float v) {
-    if constexpr (std::is_same<T, float>::value) return v;
-    else return (half_t)fminf(fmaxf(v, -65504.0f), 65504.0f);
-}
-template <typename T> __device__ __forceinline__ T filler_mark() { return (T)__builtin_inff(); }
-
-template <typename T> struct Quad;
-template <> struct Quad<float> { typedef float __attribute__((ext_vector_type(4), aligned(4))) type; };
-template <> struct Quad<half_t> { typedef half_t __attribute__((ext_vector_type(4), aligned(4))) type; };
-// a multi-dword global access needs dword alignment: f32 always has it, f16 by the address
-template <typename T> __device__ __forceinline__ bool quad_ok(const T* p) { return sizeof(T) == 4 || (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
-template <typename T> __device__ __forceinline__ void load4(const T* p, T (&v)[4]) {
-    if (quad_ok(p)) {
-        const typename Quad<T>::type w = *reinterpret_cast<const typename Quad<T>::type*>(p);
-        v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
-    } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) v[t] = p[t];
-    }
-}
-template <typename T> __device__ __forceinline__ void store4(T* p, const T (&v)[4]) {
-    if (quad_ok(p)) {
-        typename Quad<T>::type w;
-        w.x = v[0]; w.y = v[1]; w.z = v[2]; w.w = v[3];
-        *reinterpret_cast<typename Quad<T>::type*>(p) = w;
-    } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) p[t] = v[t];
-    }
-}
-
-// NRLDPCDecoder.m:236-239 for one position: the buffer takes sum + buffer (one f32 add) in its own element type and the decoder's
-// LLR is what the buffer now holds
-template <typename HbT> __device__ __forceinline__ float combine(float sum, HbT& h) {
-    h = narrow<HbT>(sum + (float)h);
-    return (float)h;
-}
-
-// The tail for the four positions pos0 .. pos0+3 of a code block's decoder input (p0 = pos0 - 2Z in d): val[t] = what this
-// transmission delivers, fill[t] = filler (+inf), inb[t] = a non-filler position of the circular buffer, keep[t] = the position
-// receives nothing and the configuration leaves such buffer entries as they are (MixRmRec::echo): read, not written.
-// HARQ && fresh (workgroup-uniform): the transport block starts a new HARQ process -- the buffer counts as +0.0 and is NOT read; every
-// non-filler position inside the circular buffer takes narrow(sum + 0), the kept ones included (they would echo the +0).
-template <bool HARQ, typename HbT, typename OutT>
-__device__ __forceinline__ void finish4(HbT* hb, OutT* out, int pos0, int p0, int ncwz, float (&val)[4], const bool (&fill)[4], const bool (&inb)[4],
-                                        const bool (&keep)[4], bool fresh) {
-    bool done = false;
-    if constexpr (HARQ) {
-        if (fresh) {
-            float zero = 0.0f;
-            asm volatile("" : "+v"(zero)); // opaque to the optimiser: sum + 0 stays an add whatever the flags, and -0 becomes +0
-            HbT h[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                h[t] = narrow<HbT>(val[t] + zero);
-                if (inb[t]) val[t] = (float)h[t];
-            }
-            if (inb[0] && inb[1] && inb[2] && inb[3]) {
-                store4(hb + p0, h);
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    if (inb[t]) hb[p0 + t] = h[t];
-            }
-            done = true;
-        }
-    }
-    if (hb && !done) {
-        if (inb[0] && inb[1] && inb[2] && inb[3] && !(keep[0] || keep[1] || keep[2] || keep[3])) {
-            HbT h[4];
-            load4(hb + p0, h);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) val[t] = combine(val[t], h[t]);
-            store4(hb + p0, h);
-        } else {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                if (inb[t]) {
-                    HbT h = hb[p0 + t];
-                    if (keep[t]) {
-                        val[t] = (float)h;
-                    } else {
-                        val[t] = combine(val[t], h);
-                        hb[p0 + t] = h;
-                    }
-                }
-        }
-    }
-    OutT o[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) o[t] = fill[t] ? filler_mark<OutT>() : narrow<OutT>(val[t]);
-    if (pos0 + 3 < ncwz) {
-        store4(out + pos0, o);
-    } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (pos0 + t < ncwz) out[pos0 + t] = o[t];
-    }
-}
-
-} // namespace
+using namespace rm_dev;
 
 // ---- rate recovery ---------------------------------------------------------------------------------------------------------------
 template <bool HARQ> struct MixRmArgs { typedef MixRmLaunch type; };
 template <> struct MixRmArgs<true> { typedef MixRmHarqLaunch type; };
-__device__ __forceinline__ const MixRmLaunch& base_of(const MixRmLaunch& a) { return a; }
-__device__ __forceinline__ const MixRmLaunch& base_of(const MixRmHarqLaunch& a) { return a.b; }
+__host__ __device__ __forceinline__ const MixRmLaunch& base_of(const MixRmLaunch& a) { return a; }
+__host__ __device__ __forceinline__ const MixRmLaunch& base_of(const MixRmHarqLaunch& a) { return a.b; }
 
 template <typename InT, typename HbT, typename OutT, bool HARQ>
 __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const typename MixRmArgs<HARQ>::type args) {
@@ -153,12 +49,7 @@ __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const type
     const int lane = threadIdx.x & 63;
     const int tile0 = w.tile0 + ((int)threadIdx.x >> 6) * MIX_RM_TILE;
     if (tile0 >= ncwz) return;
-    const int lo_f = c.Kp - 2 * Z > 0 ? c.Kp - 2 * Z : 0, hi_f = c.K - 2 * Z; // fillers (NRLDPCDecoder.m:224)
-    const int f_hi = hi_f < N_cb ? hi_f : N_cb;
-    const int F = f_hi > lo_f ? f_hi - lo_f : 0;
-    const int P = N_cb - F;
-    auto nf = [&](int x) { int d = x - lo_f; d = d < 0 ? 0 : (d > F ? F : d); return x - d; };
-    const int nfk0 = nf(c.k0);
+    const RmGeom geo(Z, c.K, c.Kp, N_cb, c.k0);
     const int E = a.e_tab[c.e_base + r];
     const int rows = E > 0 ? E / Qm : 1;
     const InT* f = static_cast<const InT*>(a.g) + c.g_off + (int64_t)tb * c.G + a.off_tab[c.e_base + r];
@@ -167,9 +58,9 @@ __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const type
     const bool echo = hb && c.echo;
     bool fresh = false; // workgroup-uniform: a workgroup is one code block of one transport block
     if constexpr (HARQ) fresh = args.is_new[mix_rm_new_index(args.tb_offs, a.recs, w)] != 0;
-    if (c.form == 0) {
+    if (c.form == RM_GENERAL) {
         // the general gather: repetitions summed in ascending k (:229-231), then the buffer
-        const int Pq = P / rows, Pr = P - Pq * rows; // a repetition is P positions of e further on
+        const int Pq = geo.P / rows, Pr = geo.P - Pq * rows;
 #pragma unroll
         for (int s = 0; s < MIX_RM_SWEEPS; ++s) {
             const int pos0 = tile0 + s * 256 + 4 * lane;
@@ -177,36 +68,7 @@ __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const type
             float val[4];
             bool fill[4], inb[4];
             const bool keep[4] = {false, false, false, false};
-            // q: index among the buffer's non-filler positions counted from k_0; e index q = i*rows + j
-            int q = -1, j = 0, i = 0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int p = pos0 + t - 2 * Z;
-                val[t] = 0.0f;
-                fill[t] = p >= lo_f && p < hi_f;
-                inb[t] = p >= 0 && !fill[t] && p < N_cb;
-                if (inb[t]) {
-                    if (q < 0) {
-                        q = nf(p) - nfk0;
-                        if (q < 0) q += P;
-                        for (int m = 1; m < Qm; ++m) i += (q >= m * rows); // q / rows when q < E = Qm * rows
-                        j = q - i * rows;
-                    }
-                    if (q < E) { // (a position that receives nothing does not touch g_tilde)
-                        float v = (float)f[j * Qm + i];
-                        int jj = j, ii = i;
-                        for (int k = q + P; k < E; k += P) {
-                            jj += Pr; ii += Pq;
-                            if (jj >= rows) { jj -= rows; ++ii; }
-                            v += (float)f[jj * Qm + ii];
-                        }
-                        val[t] = v;
-                    }
-                    ++q; ++j;
-                    if (j == rows) { j = 0; ++i; }
-                    if (q == P) { q = 0; j = 0; i = 0; }
-                }
-            }
+            gather_general(geo, f, pos0 - 2 * Z, N_cb, E, rows, Qm, Pq, Pr, val, fill, inb);
             finish4<HARQ>(hb, out, pos0, pos0 - 2 * Z, ncwz, val, fill, inb, keep, fresh);
         }
         return;
@@ -222,12 +84,9 @@ __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const type
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int p = pos0 + t - 2 * Z;
-            fill[t] = p >= lo_f && p < hi_f;
+            fill[t] = geo.filler(p);
             inb[t] = p >= 0 && p < N_cb && !fill[t];
-            int d = p - lo_f;
-            d = d < 0 ? 0 : (d > F ? F : d);
-            int q = p - d - nfk0;
-            q += q < 0 ? P : 0;
+            const int q = geo.q_of(p);
             int i = 0;
             for (int m = 1; m < Qm; ++m) i += (q >= m * rows);
             const int j = q - i * rows;
@@ -243,84 +102,24 @@ __global__ __launch_bounds__(256) void nrldpc_mix_rate_recover_kernel(const type
     }
 }
 
-hipError_t launch_mix_rate_recover(const MixRmLaunch& a, hipStream_t stream) {
+template <bool HARQ> static hipError_t launch_mix_rm(const typename MixRmArgs<HARQ>::type& args, hipStream_t stream) {
+    const MixRmLaunch& a = base_of(args);
     if (a.n_wg <= 0) return hipSuccess;
-    const dim3 grid(a.n_wg), block(256);
-    auto with_out = [&](auto in, auto hb) {
-        typedef decltype(in) InT;
-        typedef decltype(hb) HbT;
-        if (a.out_f16) hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, half_t, false>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, float, false>), grid, block, 0, stream, a);
-    };
-    auto with_hb = [&](auto in) {
-        if (a.harq && a.harq_f16) with_out(in, half_t{});
-        else with_out(in, float{}); // (without a buffer its type is never used)
-    };
-    if (a.in_f16) with_hb(half_t{});
-    else with_hb(float{});
+    rm_with_types(a.in_f16, a.harq && a.harq_f16, a.out_f16, [&](auto in, auto hb, auto out) {
+        hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<decltype(in), decltype(hb), decltype(out), HARQ>), dim3(a.n_wg), dim3(256), 0, stream, args);
+    });
     return hipGetLastError();
 }
+
+hipError_t launch_mix_rate_recover(const MixRmLaunch& a, hipStream_t stream) { return launch_mix_rm<false>(a, stream); }
 
 hipError_t launch_mix_rate_recover_harq(const MixRmHarqLaunch& a, hipStream_t stream) {
     if (a.b.n_wg <= 0) return hipSuccess;
     if (!a.b.harq || !a.is_new || !a.tb_offs) return hipErrorInvalidValue; // (the C ABI never gets here: it launches the plain kernel)
-    const dim3 grid(a.b.n_wg), block(256);
-    auto with_out = [&](auto in, auto hb) {
-        typedef decltype(in) InT;
-        typedef decltype(hb) HbT;
-        if (a.b.out_f16) hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, half_t, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((nrldpc_mix_rate_recover_kernel<InT, HbT, float, true>), grid, block, 0, stream, a);
-    };
-    auto with_hb = [&](auto in) {
-        if (a.b.harq_f16) with_out(in, half_t{});
-        else with_out(in, float{});
-    };
-    if (a.b.in_f16) with_hb(half_t{});
-    else with_hb(float{});
-    return hipGetLastError();
+    return launch_mix_rm<true>(a, stream);
 }
 
 // ---- CRC stage -------------------------------------------------------------------------------------------------------------------
-namespace {
-
-// v * M over GF(2), M = 24 columns (zero beyond the CRC length) in device memory; every lane calls this (wave-uniform control flow):
-// lane b fetches column b once and the 24 columns are then broadcast with v_readlane
-__device__ __forceinline__ uint32_t gf2_apply(const uint32_t* M, uint32_t v) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t mine = M[lane < 24 ? lane : 0];
-    uint32_t o = 0;
-#pragma unroll
-    for (int b = 0; b < 24; ++b) o ^= (0u - ((v >> b) & 1u)) & (uint32_t)__builtin_amdgcn_readlane((int)mine, b);
-    return o;
-}
-
-// CRC remainder of `len` bits (one per byte, in LDS) by one wave; every lane returns the result.
-// pl.chunk bits per lane with 64 * chunk >= len; the shortfall acts as leading zeros.
-__device__ __forceinline__ uint32_t wave_crc(const uint8_t* bits, int len, const CrcPlan& pl) {
-    const int lane = threadIdx.x & 63;
-    const int chunk = pl.chunk;
-    const int pad = 64 * chunk - len;
-    const uint32_t top = 1u << (pl.L - 1), mask = (1u << pl.L) - 1u, poly = pl.poly & mask;
-    uint32_t reg = 0;
-    const int i0 = lane * chunk - pad;
-#pragma unroll 4
-    for (int i = i0 < 0 ? 0 : i0; i < i0 + chunk; ++i) {
-        const uint32_t fb = ((reg & top) ? 1u : 0u) ^ (bits[i] & 1u);
-        reg = (reg << 1) & mask;
-        reg ^= fb ? poly : 0u;
-    }
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const uint32_t right = __shfl_down(reg, 1 << s, 64);
-        reg = gf2_apply(pl.shiftmat[s], reg) ^ right;
-    }
-    return __shfl(reg, 0, 64);
-}
-
-__host__ __device__ __forceinline__ int mix_row_capacity(int K) { return ((K + 15) & ~15) + 48; }
-
-} // namespace
-
 template <bool HARQ> struct MixCrcArgs { typedef MixCrcLaunch type; };
 template <> struct MixCrcArgs<true> { typedef MixCrcHarqLaunch type; };
 __device__ __forceinline__ const MixCrcLaunch& base_of(const MixCrcLaunch& a) { return a; }
@@ -338,7 +137,7 @@ __global__ __launch_bounds__(256) void nrldpc_mix_crc_check_kernel(const typenam
     const MixCrcRec& c = a.recs[cfg];
     const int tb = (int)blockIdx.x - a.prefix[cfg];
     const int C = c.C, K = c.K, Kp = c.Kp;
-    const int cap = mix_row_capacity(a.k_max); // one stride for every configuration: the carve-up below stays 16-byte aligned
+    const int cap = row_capacity(a.k_max); // one stride for every configuration: the carve-up below stays 16-byte aligned
     uint8_t* base = reinterpret_cast<uint8_t*>(lds) + (size_t)wave * cap;
     int* cb_fail = reinterpret_cast<int*>(lds + (size_t)nw * cap);  // [c_max]
     uint32_t* part = reinterpret_cast<uint32_t*>(cb_fail + a.c_max); // [c_max] TB-polynomial remainder per segment
@@ -395,7 +194,7 @@ __global__ __launch_bounds__(256) void nrldpc_mix_crc_check_kernel(const typenam
 
 hipError_t launch_mix_crc_check(const MixCrcLaunch& a, hipStream_t stream) {
     if (a.n_tb_total <= 0) return hipSuccess;
-    const size_t lds = (size_t)a.waves * mix_row_capacity(a.k_max) + 8 * (size_t)a.c_max + 16;
+    const size_t lds = (size_t)a.waves * row_capacity(a.k_max) + 8 * (size_t)a.c_max + 16;
     hipLaunchKernelGGL(nrldpc_mix_crc_check_kernel<false>, dim3(a.n_tb_total), dim3(64 * a.waves), lds, stream, a);
     return hipGetLastError();
 }
@@ -403,7 +202,7 @@ hipError_t launch_mix_crc_check(const MixCrcLaunch& a, hipStream_t stream) {
 hipError_t launch_mix_crc_check_harq(const MixCrcHarqLaunch& a, hipStream_t stream) {
     if (a.b.n_tb_total <= 0) return hipSuccess;
     if (!a.b.cb_pass) return hipErrorInvalidValue; // (refused by the C ABI before it gets here)
-    const size_t lds = (size_t)a.b.waves * mix_row_capacity(a.b.k_max) + 8 * (size_t)a.b.c_max + 16;
+    const size_t lds = (size_t)a.b.waves * row_capacity(a.b.k_max) + 8 * (size_t)a.b.c_max + 16;
     hipLaunchKernelGGL(nrldpc_mix_crc_check_kernel<true>, dim3(a.b.n_tb_total), dim3(64 * a.b.waves), lds, stream, a);
     return hipGetLastError();
 }

@@ -11,16 +11,18 @@
 // e[q], e[q+P], e[q+2P], ... (P = non-filler positions in the buffer), added in ascending order -- the
 // reference's accumulation order -- and e[k] = f[(k mod E/Qm)*Qm + k div (E/Qm)].  HBM-bound gather:
 // every g_tilde word is read exactly once (reads of one block interleave Qm streams), every output word
-// written once.
+// written once.  The geometry (RmGeom; the fast kernel forms its own), the fill part's tile skip and the launch rule are the one
+// copy in nrldpc_rm_core.h that nrldpc_ratematch_ex.hip and nrldpc_mix.hip run too; the gather bodies and the tail are this unit's own.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <utility>
 
 #include "nrldpc_kernels.h"
+#include "nrldpc_rm_core.h"
 
 namespace nrldpc {
+using namespace rm_dev;
 
 template <class F, int... I> __device__ __forceinline__ void rm_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
@@ -45,16 +47,10 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_kernel(const RmArgs a
     const int lane = threadIdx.x & 63;
     const int tile0 = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RR_TILE;
     if (tile0 >= ncwz) return;
-    const int lo_f = a.Kp - 2 * a.Z > 0 ? a.Kp - 2 * a.Z : 0, hi_f = a.K - 2 * a.Z; // fillers (:224)
-    // fillers that lie inside the circular buffer, and non-filler count before a position
-    const int f_hi = hi_f < a.N_cb ? hi_f : a.N_cb;
-    const int F = f_hi > lo_f ? f_hi - lo_f : 0;
-    const int P = a.N_cb - F;
-    auto nf = [&](int x) { int c = x - lo_f; c = c < 0 ? 0 : (c > F ? F : c); return x - c; };
-    const int nfk0 = nf(a.k0);
+    const RmGeom geo(a.Z, a.K, a.Kp, a.N_cb, a.k0);
     const int E = a.E[r];
     const int rows = E > 0 ? E / a.Qm : 1;
-    const int Pq = P / rows, Pr = P - Pq * rows;  // a repetition is P positions of e further on
+    const int Pq = geo.P / rows, Pr = geo.P - Pq * rows;
     const float* f = a.g + (size_t)tb * a.G + a.off[r];
     float* hb = a.harq ? a.harq + (size_t)blk * a.N_cb : nullptr;
     OutT* out = static_cast<OutT*>(a.out) + (size_t)blk * ncwz;
@@ -63,25 +59,25 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_kernel(const RmArgs a
     for (int s = 0; s < RR_PAIRS; ++s) {
         const int pos0 = tile0 + s * 128 + 2 * lane;
         if (pos0 >= ncwz) break;
+        // its own copy of the walk of gather_general (nrldpc_rm_core.h), at width 2 and with the buffer inside: shared, 2 more VGPRs
         OutT o[2];
-        // q: index among the buffer's non-filler positions counted from k_0; e index q = i*rows + j
         int q = -1, j = 0, i = 0;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int p = pos0 + t - 2 * a.Z;
             float val = 0.0f;
-            const bool filler = (p >= lo_f && p < hi_f);
+            const bool filler = geo.filler(p);
             if (p >= 0 && !filler && p < a.N_cb) {
                 if (q < 0) {
-                    q = nf(p) - nfk0;
-                    if (q < 0) q += P;
-                    for (int m = 1; m < a.Qm; ++m) i += (q >= m * rows); // q / rows when q < E = Qm * rows
+                    q = geo.nf(p) - geo.nfk0;
+                    if (q < 0) q += geo.P;
+                    for (int m = 1; m < a.Qm; ++m) i += (q >= m * rows);
                     j = q - i * rows;
                 }
                 if (q < E) {
                     val = f[j * a.Qm + i];
                     int jj = j, ii = i;
-                    for (int k = q + P; k < E; k += P) { // soft combining of repetitions, ascending k (:229-231)
+                    for (int k = q + geo.P; k < E; k += geo.P) {
                         jj += Pr; ii += Pq;
                         if (jj >= rows) { jj -= rows; ++ii; }
                         val += f[jj * a.Qm + ii];
@@ -93,9 +89,8 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_kernel(const RmArgs a
                 }
                 ++q; ++j;
                 if (j == rows) { j = 0; ++i; }
-                if (q == P) { q = 0; j = 0; i = 0; }
+                if (q == geo.P) { q = 0; j = 0; i = 0; }
             }
-            // (fillers inside the buffer: the reference keeps NaN there; the position is forced to +inf every time)
             o[t] = to_out<OutT>(filler ? __builtin_inff() : val);
         }
         if (vec) {
@@ -113,6 +108,8 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_kernel(const RmArgs a
 // 512 positions, most of them divergent control flow around the repetition walk, and runs at the rate it can issue them
 // (0.46 of the HBM roofline); this one computes both positions of a pair with selects and clamps the load index of a
 // position that receives nothing.  Same values: a position takes exactly one e(k) or none.
+// Its own geometry and body: through RmGeom and a shared body it measured 0.2 % slower at 64QAM with a buffer, outside the parent's own
+// spread of 0.07 % (profiles/r08_stage_refactor_isa.txt).
 template <typename OutT, int QM>
 __global__ __launch_bounds__(256) void nrldpc_rate_recover_fast_kernel(const RmArgs a) {
     const int blk = blockIdx.y;
@@ -201,12 +198,7 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_scatter_kernel(const 
     const int blk = blockIdx.y;
     const int tb = blk / a.C, r = blk - tb * a.C;
     const int ncwz = 2 * a.Z + a.N;
-    const int lo_f = a.Kp - 2 * a.Z > 0 ? a.Kp - 2 * a.Z : 0, hi_f = a.K - 2 * a.Z;
-    const int f_hi = hi_f < a.N_cb ? hi_f : a.N_cb;
-    const int F = f_hi > lo_f ? f_hi - lo_f : 0;
-    const int P = a.N_cb - F;
-    int nfk0 = a.k0 - lo_f;
-    nfk0 = a.k0 - (nfk0 < 0 ? 0 : (nfk0 > F ? F : nfk0));
+    const RmGeom geo(a.Z, a.K, a.Kp, a.N_cb, a.k0);
     const int E = a.E[r];
     const int rows = E / QM;
     float* hb = a.harq ? a.harq + (size_t)blk * a.N_cb : nullptr;
@@ -236,12 +228,9 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_scatter_kernel(const 
 #pragma unroll
         for (int i = 0; i < QM; ++i) {
             // non-filler index of e(i*rows + j0) counted from 0, then its position in d (fillers skipped), then in the core's input
-            int n = i * rows + j0 + nfk0;
-            n -= n >= P ? P : 0;
-            const int p = n < lo_f ? n : n + F;
-            // the J values are neighbours in d unless the run crosses the end of the buffer or the filler gap
-            const bool run = nj == J && n + J <= P && (n >= lo_f || n + J <= lo_f);
-            if (run) {
+            const int n = geo.n_of(i * rows + j0);
+            const int p = geo.pos_at(n);
+            if (nj == J && geo.whole_run(n, J)) {
                 float val[J];
 #pragma unroll
                 for (int t = 0; t < J; ++t) val[t] = v[t * QM + i];
@@ -268,8 +257,8 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_scatter_kernel(const 
             } else {
                 for (int t = 0; t < nj; ++t) {
                     int nn = n + t;
-                    nn -= nn >= P ? P : 0;
-                    const int pp = nn < lo_f ? nn : nn + F;
+                    nn -= nn >= geo.P ? geo.P : 0;
+                    const int pp = geo.pos_at(nn);
                     float val = v[t * QM + i];
                     if (hb) { val += hb[pp]; hb[pp] = val; }
                     out[2 * a.Z + pp] = to_out<OutT>(val);
@@ -283,28 +272,7 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_scatter_kernel(const 
     const int wave = ((int)blockIdx.x - in_blocks) * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int tile0 = wave * RR_FILL_TILE;
     if (tile0 >= ncwz) return;
-    // d positions [c0, c1) (cyclically, in non-filler index space [n0, n0 + E)) are covered
-    auto covered = [&](int p) -> bool { // p: position in d, 0 <= p < N_cb, not a filler
-        int c = p - lo_f;
-        c = c < 0 ? 0 : (c > F ? F : c);
-        int q = p - c - nfk0;
-        q += q < 0 ? P : 0;
-        return q < E;
-    };
-    {
-        // wave-uniform skip: the tile lies inside one stretch of d between two boundaries and that stretch is covered
-        const int x0 = tile0, x1 = (tile0 + RR_FILL_TILE < ncwz ? tile0 + RR_FILL_TILE : ncwz) - 1; // inclusive
-        const int p0 = x0 - 2 * a.Z, p1 = x1 - 2 * a.Z;
-        bool plain = p0 >= 0 && p1 < a.N_cb && !(p1 >= lo_f && p0 < hi_f); // no punctured column, nothing beyond the buffer, no filler
-        if (plain) {
-            // covered positions form a cyclic interval of non-filler indices: both ends covered and the same distance apart in q as in p
-            int c0 = p0 - lo_f; c0 = c0 < 0 ? 0 : (c0 > F ? F : c0);
-            int c1 = p1 - lo_f; c1 = c1 < 0 ? 0 : (c1 > F ? F : c1);
-            int q0 = p0 - c0 - nfk0; q0 += q0 < 0 ? P : 0;
-            int q1 = p1 - c1 - nfk0; q1 += q1 < 0 ? P : 0;
-            if (q0 < E && q1 < E && q1 - q0 == p1 - p0) return;
-        }
-    }
+    if (fill_tile_covered(geo, tile0, RR_FILL_TILE, ncwz, a.Z, a.N_cb, E)) return;
     const bool vec = (ncwz % 2) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 7) == 0;
 #pragma unroll
     for (int s = 0; s < RR_FILL_TILE / 128; ++s) {
@@ -315,9 +283,9 @@ __global__ __launch_bounds__(256) void nrldpc_rate_recover_scatter_kernel(const 
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int p = pos0 + t - 2 * a.Z;
-            const bool filler = p >= lo_f && p < hi_f;
+            const bool filler = geo.filler(p);
             const bool inbuf = p >= 0 && p < a.N_cb && !filler;
-            skip[t] = (inbuf && covered(p)) || pos0 + t >= ncwz;
+            skip[t] = (inbuf && geo.covered(p, E)) || pos0 + t >= ncwz;
             float val = 0.0f;
             if (hb && inbuf && !skip[t]) val = hb[p]; // :236-239 with nothing received: the buffer as it is
             o[t] = to_out<OutT>(filler ? __builtin_inff() : val);
@@ -351,12 +319,7 @@ __global__ __launch_bounds__(256) void nrldpc_rate_match_kernel(const TxRmArgs a
     const int rows = E / QM;
     const int j0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (j0 >= rows) return;
-    const int lo_f = a.Kp - 2 * a.Z > 0 ? a.Kp - 2 * a.Z : 0, hi_f = a.K - 2 * a.Z;
-    const int f_hi = hi_f < a.N_cb ? hi_f : a.N_cb;
-    const int F = f_hi > lo_f ? f_hi - lo_f : 0;
-    const int P = a.N_cb - F;
-    auto nf = [&](int p) { int c = p - lo_f; c = c < 0 ? 0 : (c > F ? F : c); return p - c; };
-    const int nfk0 = nf(a.k0);
+    const RmGeom geo(a.Z, a.K, a.Kp, a.N_cb, a.k0);
     const uint8_t* cw = a.cw + (size_t)blk * (2 * a.Z + a.N) + 2 * a.Z;
     const int nj = rows - j0 < 4 ? rows - j0 : 4; // j of this thread that exist
     uint32_t run[QM]; // byte t of run[i] = e(i*rows + j0 + t)
@@ -364,25 +327,25 @@ __global__ __launch_bounds__(256) void nrldpc_rate_match_kernel(const TxRmArgs a
     // and the index arithmetic is adds and compares.  With repetition k wraps around P: a division and a modulo per run and per
     // gathered byte, ~35 VALU instructions each -- as one code path for both (the first version) the kernel issued 233 VALU
     // instructions per thread for its 8 output bytes and ran at the rate it could issue them, not at the rate of its bytes.
-    const bool rep = E > P; // uniform over the workgroup
+    const bool rep = E > geo.P; // uniform over the workgroup
 #pragma unroll
     for (int i = 0; i < QM; ++i) {
         const int k = i * rows + j0;
         int q, kend; // q: position among the buffer's non-filler bits; kend: first k of the next repetition
-        if (rep) { const int d = k / P; q = k - d * P + nfk0; kend = P * (d + 1); }
-        else { q = k + nfk0; kend = P; }
-        if (q >= P) q -= P;
+        if (rep) { const int d = k / geo.P; q = k - d * geo.P + geo.nfk0; kend = geo.P * (d + 1); }
+        else { q = k + geo.nfk0; kend = geo.P; }
+        if (q >= geo.P) q -= geo.P;
         // four consecutive e indices are four consecutive bytes when the run stays below P in k (no repetition wrap) and
         // in q (no buffer wrap) and on one side of the filler gap
-        if (nj == 4 && k + 3 < kend && q + 3 < P && (q >= lo_f || q + 3 < lo_f)) {
-            run[i] = *reinterpret_cast<const u32_unaligned*>(cw + (q < lo_f ? q : q + F)) & 0x01010101u;
+        if (nj == 4 && k + 3 < kend && q + 3 < geo.P && (q >= geo.lo_f || q + 3 < geo.lo_f)) {
+            run[i] = *reinterpret_cast<const u32_unaligned*>(cw + (q < geo.lo_f ? q : q + geo.F)) & 0x01010101u;
         } else {
             uint32_t w = 0;
             for (int t = 0; t < nj; ++t) {
                 const int kk = k + t;
-                int qq = (rep ? kk % P : kk) + nfk0;
-                if (qq >= P) qq -= P;
-                w |= (uint32_t)(cw[qq < lo_f ? qq : qq + F] & 1u) << (8 * t);
+                int qq = (rep ? kk % geo.P : kk) + geo.nfk0;
+                if (qq >= geo.P) qq -= geo.P;
+                w |= (uint32_t)(cw[qq < geo.lo_f ? qq : qq + geo.F] & 1u) << (8 * t);
             }
             run[i] = w;
         }
@@ -433,63 +396,30 @@ hipError_t launch_rate_match(const TxRmArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-template <typename OutT> static void launch_rr_fast(const RmArgs& a, dim3 grid, hipStream_t stream) {
-    switch (a.Qm) {
-        case 1: hipLaunchKernelGGL((nrldpc_rate_recover_fast_kernel<OutT, 1>), grid, dim3(256), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((nrldpc_rate_recover_fast_kernel<OutT, 2>), grid, dim3(256), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((nrldpc_rate_recover_fast_kernel<OutT, 4>), grid, dim3(256), 0, stream, a); break;
-        case 6: hipLaunchKernelGGL((nrldpc_rate_recover_fast_kernel<OutT, 6>), grid, dim3(256), 0, stream, a); break;
-        default: hipLaunchKernelGGL((nrldpc_rate_recover_fast_kernel<OutT, 8>), grid, dim3(256), 0, stream, a); break;
-    }
-}
-
-template <typename OutT> static void launch_rr_scatter(const RmArgs& a, int emax, hipStream_t stream) {
+template <typename OutT> static void launch_rr(const RmArgs& a, const RmRule& rule, hipStream_t stream) {
     const int ncwz = 2 * a.Z + a.N;
-    const int fill_blocks = (ncwz + 4 * RR_FILL_TILE - 1) / (4 * RR_FILL_TILE);
-    auto go = [&](auto qc) {
-        constexpr int QM = decltype(qc)::value;
-        const int rows = emax / QM;
-        const int in_blocks = (rows + 256 * RrJ<QM>::J - 1) / (256 * RrJ<QM>::J);
-        hipLaunchKernelGGL((nrldpc_rate_recover_scatter_kernel<OutT, QM>), dim3(in_blocks + fill_blocks, a.n_tb * a.C), dim3(256), 0, stream, a, in_blocks);
-    };
-    switch (a.Qm) {
-        case 1: go(std::integral_constant<int, 1>{}); break;
-        case 2: go(std::integral_constant<int, 2>{}); break;
-        case 4: go(std::integral_constant<int, 4>{}); break;
-        case 6: go(std::integral_constant<int, 6>{}); break;
-        default: go(std::integral_constant<int, 8>{}); break;
+    const dim3 grid((ncwz + 4 * RR_TILE - 1) / (4 * RR_TILE), a.n_tb * a.C);
+    if (rule.form == RM_GENERAL) {
+        hipLaunchKernelGGL(nrldpc_rate_recover_kernel<OutT>, grid, dim3(256), 0, stream, a);
+    } else if (rule.form == RM_SCATTER) {
+        const int fill_blocks = (ncwz + 4 * RR_FILL_TILE - 1) / (4 * RR_FILL_TILE);
+        rm_per_qm(a.Qm, [&](auto qc) {
+            constexpr int QM = decltype(qc)::value;
+            const int rows = rule.emax / QM;
+            const int in_blocks = (rows + 256 * RrJ<QM>::J - 1) / (256 * RrJ<QM>::J);
+            hipLaunchKernelGGL((nrldpc_rate_recover_scatter_kernel<OutT, QM>), dim3(in_blocks + fill_blocks, a.n_tb * a.C), dim3(256), 0, stream, a, in_blocks);
+        });
+    } else {
+        rm_per_qm(a.Qm, [&](auto qc) {
+            hipLaunchKernelGGL((nrldpc_rate_recover_fast_kernel<OutT, decltype(qc)::value>), grid, dim3(256), 0, stream, a);
+        });
     }
 }
 
 hipError_t launch_rate_recover(const RmArgs& a, hipStream_t stream) {
-    const int ncwz = 2 * a.Z + a.N;
-    const int per_block = 4 * RR_TILE;
-    dim3 grid((ncwz + per_block - 1) / per_block, a.n_tb * a.C);
-    // non-filler positions of the circular buffer: a code block with more bits than that repeats (soft combining walk)
-    const int lo_f = a.Kp - 2 * a.Z > 0 ? a.Kp - 2 * a.Z : 0, hi_f = a.K - 2 * a.Z;
-    const int f_hi = hi_f < a.N_cb ? hi_f : a.N_cb;
-    const int P = a.N_cb - (f_hi > lo_f ? f_hi - lo_f : 0);
-    static const bool force_general = getenv("NRLDPC_RR_GENERAL") != nullptr; // A/B: force the general kernel
-    // the input-driven form where it measured faster than the gather -- with the HARQ buffer and Q_m <= 2: -25 % on the headline code;
-    // it loses 6-17 % without the buffer, 21 % at 64QAM with it, and 2.4 x on kilobyte-sized blocks (profiles/r06_rate_recover_scatter_ab.txt).
-    // NRLDPC_RR_SCATTER=0 / 1 forces the gather / the scatter wherever it applies (A/B)
-    static const int env_scatter = getenv("NRLDPC_RR_SCATTER") ? atoi(getenv("NRLDPC_RR_SCATTER")) : -1;
-    bool repeats = force_general;
-    int emax = 0;
-    for (int r = 0; r < a.C; ++r) { repeats = repeats || a.E[r] > P; emax = a.E[r] > emax ? a.E[r] : emax; }
-    const bool qm_ok = a.Qm == 1 || a.Qm == 2 || a.Qm == 4 || a.Qm == 6 || a.Qm == 8;
-    const bool scatter = env_scatter >= 0 ? env_scatter != 0 : (a.harq != nullptr && a.Qm <= 2 && a.N >= 4096);
-    if (!repeats && qm_ok && scatter) {
-        if (a.out_f16) launch_rr_scatter<__half>(a, emax, stream);
-        else launch_rr_scatter<float>(a, emax, stream);
-    } else if (!repeats && qm_ok) {
-        if (a.out_f16) launch_rr_fast<__half>(a, grid, stream);
-        else launch_rr_fast<float>(a, grid, stream);
-    } else if (a.out_f16) {
-        hipLaunchKernelGGL(nrldpc_rate_recover_kernel<__half>, grid, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL(nrldpc_rate_recover_kernel<float>, grid, dim3(256), 0, stream, a);
-    }
+    const RmRule rule = rm_launch_rule(RmGeom(a.Z, a.K, a.Kp, a.N_cb, a.k0), a.E, a.C, a.Qm, a.N, a.harq != nullptr, rm_env_switches());
+    if (a.out_f16) launch_rr<__half>(a, rule, stream);
+    else launch_rr<float>(a, rule, stream);
     return hipGetLastError();
 }
 

@@ -2,14 +2,18 @@
 they reach (tests/test_rr_cases.py, CPU): the receive-side twin of tests/tx_cases.py.
 
 Rate recovery exists in three units -- "f32": csrc/nrldpc_ratematch.hip (nrldpc_rate_recover_dev, a lane owns a PAIR of positions),
-"ex": csrc/nrldpc_ratematch_ex.hip (nrldpc_rate_recover_ex_dev, a QUAD), "mix": csrc/nrldpc_mix.hip (nrldpc_mix_rate_recover[_harq]_dev,
-quads from a table) -- and each picks its kernel, and inside it its code path, from sizes, from where a group of positions lies
-relative to the boundaries of a code block (the 2Z punctured columns, the filler gap, the end of the circular buffer, the end of E,
-the wrap at k_0, a change of interleaver row) and from the ALIGNMENT of the addresses it is given.  The census below restates
-those conditions from the kernel sources -- no part of it runs a kernel -- so that the list of sets can be held to "every class is
+"ex": csrc/nrldpc_ratematch_ex.hip (nrldpc_rate_recover_ex_dev, a QUAD), "mix": csrc/nrldpc_mix.hip
+(nrldpc_mix_rate_recover[_harq]_dev, quads from a table) -- and each picks its kernel, and inside it its code path, from sizes,
+from where a group of positions lies relative to the boundaries of a code block (the 2Z punctured columns, the filler gap, the end
+of the circular buffer, the end of E, the wrap at k_0, a change of interleaver row) and from the ALIGNMENT of the addresses it is
+given.  The conditions the units share live once, in csrc/nrldpc_rm_core.h: the geometry (RmGeom), the launch rule (rm_launch_rule
+-- tests/test_rm_rule_host.py holds launch_form and mix_form below to it on the CPU), the general gather of ex and mix
+(gather_general; the f32 unit's general kernel keeps a copy of the walk) and the tail finish4 with its access widths; the
+branch-free gather, the scatter's input part, the fill loops and the f32 unit's tail are in the units.  The census below restates
+those conditions from the sources -- no part of it runs a kernel -- so that the list of sets can be held to "every class is
 reached" on the CPU.  Derived parameters come from testbench_ref.derive through tx_cases.derive.  The last section ("the device
-side") is what the GPU test and the switch child share to run a set on the device and compare it with the model; the census does not
-use it, and it imports torch only when called.
+side") is what the GPU test and the switch child share to run a set on the device and compare it with the model; the census does
+not use it, and it imports torch only when called.
 
 A class is (unit, form, Q_m, feature).  Forms: "general" (the repetition walk), "fast" (the no-repetition gather), "scatter" (the
 input-driven form, units f32 and ex).  Features:
