@@ -429,7 +429,8 @@ int nrldpc_crc_check_harq_dev(const nrldpc_tb_params* p, const uint8_t* d_c_hat,
  * rv_id.  A plan stays immutable.  rv_id only moves k_0, and no field of nrldpc_mix_layout depends on it: a HARQ receiver holds one
  *   plan per redundancy version (per distinct tuple of rv_ids, at most a handful) over the SAME packed arrays.
  *
- * Out of scope: pool variants, the transmit side, the MEX gateway, a G that changes between retransmissions. */
+ * Out of scope: pool variants, a one-launch mixed encoder (the transmit side itself is nrldpc_mix_tx_*, below), the MEX gateway, a G
+ * that changes between retransmissions. */
 typedef struct nrldpc_mix* nrldpc_mix_handle;
 
 /* element offsets of configuration i inside the packed arrays; entry [n] holds the totals */
@@ -470,6 +471,54 @@ int nrldpc_mix_crc_check_harq_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, u
  * code_block_concatenation (NRLDPCEncoder.m:168-256): d_cw [n_tb*C][ncols*Z] -> d_g [n_tb][G]. */
 int nrldpc_crc_attach_dev(const nrldpc_tb_params* p, const uint8_t* d_a, int32_t n_tb, uint8_t* d_c, void* stream);
 int nrldpc_rate_match_dev(const nrldpc_tb_params* p, const uint8_t* d_cw, int32_t n_tb, uint8_t* d_g, void* stream);
+
+/* ---- mixed transport-block batches, transmit side: CRC attach and rate matching in one launch each ----------------------------
+ * The transmit mirror of nrldpc_mix_*: for a batch whose transport blocks differ in (BG, A, G, Q_m, rv_id, LBRM, C), a TRANSMIT PLAN
+ * is built once from n parameter blocks and n transport-block counts, is immutable, owns its device-side tables, and serves three
+ * stage calls that take the plan and base pointers only.  nrldpc_mix_tx_handle is a type of its own; the receive plan, its layout
+ * and nrldpc_mix_create are unchanged.  Added without a revision bump (NRLDPC_ABI_VERSION stays 6): a binding finds the functions by
+ * symbol.
+ *
+ * Layout.  Only the payload array a ([n_tb][A] bytes per configuration) is new: a_off[0] = 0, a_off[i+1] = round_up(a_off[i] +
+ *   n_tb[i]*A_i, 16), entry [n] = the total (nrldpc_mix_tx_layout; host only).  Every other transmit array reuses a field of
+ *   nrldpc_mix_layout element for element: code blocks c [n_tb*C][K] = field c_hat, codeword bytes [n_tb*C][ncols*Z] = field cw,
+ *   rate-matched bits g [n_tb][G] = field g -- a loop-back hands g to a channel and on to the receive plan of the same (p, n_tb).
+ *
+ * Semantics, by equality.  In every segment
+ *   nrldpc_mix_tx_crc_attach_dev leaves in c  what nrldpc_crc_attach_dev(&p[i], a + a_off[i], n_tb[i], c + off[i].c_hat, stream) leaves,
+ *   nrldpc_mix_tx_encode_dev     leaves in cw what nrldpc_encode_dev(h[i], c + off[i].c_hat, n_tb[i]*C_i, cw + off[i].cw, stream) leaves,
+ *   nrldpc_mix_tx_rate_match_dev leaves in g  what nrldpc_rate_match_dev(&p[i], cw + off[i].cw, n_tb[i], g + off[i].g, stream) leaves,
+ *   bit for bit.  Only bit 0 of an input byte is read and every output byte is 0 or 1.  Gap elements are never read or written; one
+ *   thread writes each output byte, no atomics: results are the same from run to run and do not depend on which configurations share
+ *   the plan or on how a mix is split into plans.  These are byte arrays: any byte address of the base pointers is served.
+ *   Attach and rate matching are ONE launch each whatever n.  The encode stage has no kernel of its own: it launches the existing
+ *   encoder once per non-empty configuration, in configuration order, on the caller's stream; h[i] may repeat for configurations that
+ *   share (BG, Z_c) and is not read for an empty one.
+ *
+ * Refusals.  nrldpc_mix_tx_layout and nrldpc_mix_tx_create refuse what nrldpc_mix_layout / nrldpc_mix_create refuse, with the same
+ *   codes and texts (" (configuration i)" appended to the single-configuration call's text; NRLDPC_ERR_ARG for negative counts or null
+ *   arrays; "too large for one launch"), and add the transmit stages' own per block: a code block shorter than the transport-block CRC
+ *   (nrldpc_crc_attach_dev's text) and a Q_m outside {1, 2, 4, 6, 8} -> NRLDPC_ERR_UNSUPPORTED.  The first broken block is the one
+ *   reported.  n == 0 or all counts zero is a valid empty plan that needs no device: every stage call on it returns NRLDPC_OK without
+ *   a launch.  Stage calls refuse, before any device call: a null plan; a null base pointer whose array is not empty; for the encode
+ *   stage, naming the configuration, a null handle of a non-empty configuration, a handle whose (BG, Z) differs from the
+ *   configuration's, a handle on another device than the plan -> NRLDPC_ERR_ARG.
+ *
+ * Concurrency.  The plan's tables are one device allocation, uploaded synchronously by nrldpc_mix_tx_create and never written again:
+ *   calls in flight on several streams may share one plan (each with its own arrays).  The stage calls only enqueue.
+ *
+ * Out of scope: a one-launch mixed encoder, pool variants, the MEX gateway, a mixed-batch channel stage. */
+typedef struct nrldpc_mix_tx* nrldpc_mix_tx_handle;
+
+/* host function, no device: a_off has n + 1 entries (elements = bytes of the payload array) */
+int nrldpc_mix_tx_layout(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int64_t* a_off);
+
+int nrldpc_mix_tx_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int32_t device_id, nrldpc_mix_tx_handle* out);
+void nrldpc_mix_tx_destroy(nrldpc_mix_tx_handle m);
+
+int nrldpc_mix_tx_crc_attach_dev(nrldpc_mix_tx_handle m, const uint8_t* d_a, uint8_t* d_c, void* stream);
+int nrldpc_mix_tx_encode_dev(nrldpc_mix_tx_handle m, const nrldpc_handle* h /* [n] */, const uint8_t* d_c, uint8_t* d_cw, void* stream);
+int nrldpc_mix_tx_rate_match_dev(nrldpc_mix_tx_handle m, const uint8_t* d_cw, uint8_t* d_g, void* stream);
 
 /* Channel leg of the Monte-Carlo loop, fused: replaces step(hMod,g), step(hChan,tx),
  * step(hDemod,rx) of plot_BLER_vs_SNR.m:130-132 -- NRModulator.m:73-81 (TS 38.211 maps, unit average power),

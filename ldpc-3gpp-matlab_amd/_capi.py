@@ -115,7 +115,9 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_set_algorithm", "nrldpc_get_algorithm", "nrldpc_pool_set_algorithm", "nrldpc_decode_cw", "nrldpc_decode_cw_dev",
            "nrldpc_modulate_dev", "nrldpc_demodulate_dev", "nrldpc_rate_recover_ex_dev", "nrldpc_awgn_dev",
            "nrldpc_mix_layout", "nrldpc_mix_create", "nrldpc_mix_destroy", "nrldpc_mix_rate_recover_dev", "nrldpc_mix_crc_check_dev",
-           "nrldpc_mix_rate_recover_harq_dev", "nrldpc_mix_crc_check_harq_dev"]
+           "nrldpc_mix_rate_recover_harq_dev", "nrldpc_mix_crc_check_harq_dev",
+           "nrldpc_mix_tx_layout", "nrldpc_mix_tx_create", "nrldpc_mix_tx_destroy", "nrldpc_mix_tx_crc_attach_dev", "nrldpc_mix_tx_encode_dev",
+           "nrldpc_mix_tx_rate_match_dev"]
 
 _lib = None
 
@@ -201,6 +203,14 @@ def load():
     if hasattr(L, "nrldpc_mix_rate_recover_harq_dev"):  # the HARQ / CBGTI forms, again without a revision bump
         L.nrldpc_mix_rate_recover_harq_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp]
         L.nrldpc_mix_crc_check_harq_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "nrldpc_mix_tx_create"):  # the transmit side of the mixed batches, again without a revision bump
+        L.nrldpc_mix_tx_layout.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), C.POINTER(C.c_int64)]
+        L.nrldpc_mix_tx_create.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), i32, C.POINTER(vp)]
+        L.nrldpc_mix_tx_destroy.argtypes = [vp]
+        L.nrldpc_mix_tx_destroy.restype = None
+        L.nrldpc_mix_tx_crc_attach_dev.argtypes = [vp, vp, vp, vp]
+        L.nrldpc_mix_tx_encode_dev.argtypes = [vp, C.POINTER(vp), vp, vp, vp]
+        L.nrldpc_mix_tx_rate_match_dev.argtypes = [vp, vp, vp, vp]
     L.nrldpc_crc_attach_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_rate_match_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_pool_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), i32, i32, C.POINTER(vp)]
@@ -657,6 +667,79 @@ class MixPlan:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.nrldpc_mix_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _mix_tx_lib():
+    L = _mix_lib()
+    if not hasattr(L, "nrldpc_mix_tx_create"):
+        raise NRLDPCError("%s has no nrldpc_mix_tx_create: the transmit side of mixed transport-block batches needs a library built "
+                          "from this tree (NRLDPC_LIB selects an older one?)" % lib_path())
+    return L
+
+
+def mix_tx_layout(params, n_tb):
+    """nrldpc_mix_tx_layout: the n + 1 byte offsets of the packed payload array a of a mix ([n]: the total).  Every other transmit
+    array uses mix_layout's fields: code blocks = c_hat, codeword bytes = cw, rate-matched bits = g.  Host function, no device needed."""
+    n, ts, nt = _mix_args(params, n_tb)
+    a_off = (C.c_int64 * (n + 1))()
+    check(_mix_tx_lib().nrldpc_mix_tx_layout(n, ts, nt, a_off))
+    return [int(x) for x in a_off]
+
+
+class MixTxPlan:
+    """nrldpc_mix_tx_*: the transmit twin of MixPlan -- an immutable plan for a batch whose transport blocks differ in
+    (BG, A, G, Q_m, rv_id, LBRM, C).  .a_off: the n + 1 byte offsets of the packed payload array; .off: the receive layout's n + 1
+    MixOffsets records, of which the transmit arrays use c_hat (code blocks), cw (codeword bytes) and g (rate-matched bits);
+    totals(): {"a", "c", "cw", "g"} -> elements to allocate.  crc_attach() and rate_match() are one launch each, whatever n; encode()
+    launches the existing encoder once per non-empty configuration.  Streams may share a plan."""
+
+    def __init__(self, params, n_tb, device_id=0):
+        self._h = C.c_void_p()
+        self._lib = L = _mix_tx_lib()
+        self.n, ts, nt = _mix_args(params, n_tb)
+        self.n_tb = [int(x) for x in n_tb]
+        self.device_id = int(device_id)
+        a_off = (C.c_int64 * (self.n + 1))()
+        check(L.nrldpc_mix_tx_layout(self.n, ts, nt, a_off))
+        self.a_off = [int(x) for x in a_off]
+        off = (MixOffsets * (self.n + 1))()
+        check(L.nrldpc_mix_layout(self.n, ts, nt, off))
+        self.off = list(off)
+        self.params = [ts[i] for i in range(self.n)]
+        self._ts = ts  # (the records above are views of this array)
+        check(L.nrldpc_mix_tx_create(self.n, ts, nt, self.device_id, C.byref(self._h)))
+
+    def totals(self):
+        """Elements (bytes) to allocate for each packed transmit array."""
+        t = self.off[self.n]
+        return {"a": self.a_off[self.n], "c": t.c_hat, "cw": t.cw, "g": t.g}
+
+    def crc_attach(self, d_a, d_c, stream=0):
+        """nrldpc_mix_tx_crc_attach_dev on raw device addresses of the packed arrays."""
+        check(self._lib.nrldpc_mix_tx_crc_attach_dev(self._h, _ptr(d_a), _ptr(d_c), C.c_void_p(stream)))
+
+    def encode(self, codecs, d_c, d_cw, stream=0):
+        """nrldpc_mix_tx_encode_dev: codecs[i] (a Codec, or None for an empty configuration) encodes configuration i's code blocks."""
+        codecs = list(codecs)
+        if len(codecs) != self.n:
+            raise NRLDPCError("one codec per configuration expected (%d), got %d." % (self.n, len(codecs)))
+        hs = (C.c_void_p * max(self.n, 1))(*[c._h if c is not None else None for c in codecs])
+        check(self._lib.nrldpc_mix_tx_encode_dev(self._h, hs, _ptr(d_c), _ptr(d_cw), C.c_void_p(stream)))
+
+    def rate_match(self, d_cw, d_g, stream=0):
+        """nrldpc_mix_tx_rate_match_dev on raw device addresses of the packed arrays."""
+        check(self._lib.nrldpc_mix_tx_rate_match_dev(self._h, _ptr(d_cw), _ptr(d_g), C.c_void_p(stream)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.nrldpc_mix_tx_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -38,6 +38,7 @@
 #include "nrldpc_modem.h"
 #include "nrldpc_ratematch_ex.h"
 #include "nrldpc_mix.h"
+#include "nrldpc_mix_tx.h"
 #include "nrldpc_rm_core.h"
 
 static_assert(sizeof(nrldpc_cw_out) == 32, "nrldpc_cw_out: the size include/nrldpc.h states");
@@ -2165,6 +2166,20 @@ int mix_fail_at(int rc, int i) {
     return rc;
 }
 
+// the checks of the single-configuration calls on one block of a mix, with their texts: check_tb_params, fill_rm_blocks, the CRC stage's own
+int mix_check_cfg(const nrldpc_tb_params* q, int32_t n_tb, int i, nrldpc::RmExArgs& blocks) {
+    int rc = check_tb_params(q);
+    if (rc) return mix_fail_at(rc, i);
+    rc = fill_rm_blocks(q, 0, blocks); // (E_r and the offsets of the code blocks inside a row of g_tilde)
+    if (rc) return mix_fail_at(rc, i);
+    if ((q->tb_crc_len != 16 && q->tb_crc_len != 24) || (q->cb_crc_len != 0 && q->cb_crc_len != 24))
+        return mix_fail_at(fail(NRLDPC_ERR_UNSUPPORTED, "CRC lengths must be 16/24 (TB) and 0/24 (CB)"), i);
+    if (q->B != q->A + q->tb_crc_len || q->C * (q->K_prime - q->cb_crc_len) != q->B)
+        return mix_fail_at(fail(NRLDPC_ERR_ARG, "B must equal A + L and C*(K' - L_cb)"), i);
+    if (n_tb < 0) return mix_fail_at(fail(NRLDPC_ERR_ARG, "negative batch"), i);
+    return NRLDPC_OK;
+}
+
 int mix_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool tables, MixHost& m) {
     if (n < 0) return fail(NRLDPC_ERR_ARG, "negative configuration count");
     if (n > 0 && (!p || !n_tb)) return fail(NRLDPC_ERR_ARG, "null array");
@@ -2175,17 +2190,9 @@ int mix_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool ta
     int64_t wg = 0, tbs = 0;
     for (int i = 0; i < n; ++i) {
         const nrldpc_tb_params* q = p + i;
-        // the checks of the single-configuration calls, with their texts: check_tb_params, fill_rm_blocks, the CRC stage's own
-        int rc = check_tb_params(q);
-        if (rc) return mix_fail_at(rc, i);
-        nrldpc::RmExArgs blocks; // (E_r and the offsets of the code blocks inside a row of g_tilde)
-        rc = fill_rm_blocks(q, 0, blocks);
-        if (rc) return mix_fail_at(rc, i);
-        if ((q->tb_crc_len != 16 && q->tb_crc_len != 24) || (q->cb_crc_len != 0 && q->cb_crc_len != 24))
-            return mix_fail_at(fail(NRLDPC_ERR_UNSUPPORTED, "CRC lengths must be 16/24 (TB) and 0/24 (CB)"), i);
-        if (q->B != q->A + q->tb_crc_len || q->C * (q->K_prime - q->cb_crc_len) != q->B)
-            return mix_fail_at(fail(NRLDPC_ERR_ARG, "B must equal A + L and C*(K' - L_cb)"), i);
-        if (n_tb[i] < 0) return mix_fail_at(fail(NRLDPC_ERR_ARG, "negative batch"), i);
+        nrldpc::RmExArgs blocks;
+        const int rc = mix_check_cfg(q, n_tb[i], i, blocks);
+        if (rc) return rc;
         const int32_t ncwz = 2 * q->Z + q->N;
         int64_t s[nrldpc::MIX_FIELDS];
         nrldpc::mix_sizes(n_tb[i], q->C, q->G, q->N_cb, ncwz, q->K, q->B, s);
@@ -2367,6 +2374,209 @@ int nrldpc_mix_crc_check_harq_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, u
     if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
     hipError_t e = nrldpc::launch_mix_crc_check_harq(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hipfail(e, "mix CRC kernel launch");
+    return NRLDPC_OK;
+}
+
+} // extern "C"
+
+// ---- mixed transport-block batches, transmit side (nrldpc_mix_tx_*; kernels: nrldpc_mix_tx.hip, tables and mapping: nrldpc_mix_tx.h) ----
+// A type of its own: the receive plan nrldpc_mix, its blob and its records are untouched.
+struct nrldpc_mix_tx {
+    int32_t n = 0, device_id = 0;
+    std::vector<nrldpc_mix_offsets> off; // n + 1: the receive layout's (c = c_hat, codeword bytes = cw, rate-matched bits = g)
+    std::vector<int64_t> a_off;          // n + 1: the payload array
+    std::vector<int32_t> bg, Z, n_cw;    // per configuration: what its encoder handle must be, and its codewords n_tb * C
+    int64_t size_a = 0, size_c = 0, size_cw = 0, size_g = 0; // elements in use (sum over configurations)
+    char* blob = nullptr;                // every device table, one allocation, written once by nrldpc_mix_tx_create
+    nrldpc::MixTxCrcLaunch crc{};
+    nrldpc::MixTxRmLaunch rm{};
+};
+
+namespace {
+
+struct MixTxHost {
+    std::vector<nrldpc_mix_offsets> off;
+    std::vector<int64_t> a_off;
+    std::vector<nrldpc::MixTxRmRec> rm;
+    std::vector<nrldpc::MixTxCrcRec> crc;
+    std::vector<int32_t> rm_prefix, tb_prefix, e_tab, off_tab;
+    int64_t used_a = 0, used_c = 0, used_cw = 0, used_g = 0;
+    int32_t k_max = 0, c_max = 0;
+};
+
+// everything the transmit plan needs, on the host.  No device call.  The refusals of mix_build, then the transmit stages' own.
+int mix_tx_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool tables, MixTxHost& m) {
+    if (n < 0) return fail(NRLDPC_ERR_ARG, "negative configuration count");
+    if (n > 0 && (!p || !n_tb)) return fail(NRLDPC_ERR_ARG, "null array");
+    m.off.assign((size_t)n + 1, nrldpc_mix_offsets{0, 0, 0, 0, 0, 0, 0});
+    m.a_off.assign((size_t)n + 1, 0);
+    m.rm_prefix.assign((size_t)n + 1, 0);
+    m.tb_prefix.assign((size_t)n + 1, 0);
+    if (tables) { m.rm.resize(n); m.crc.resize(n); }
+    int64_t wg = 0, wg_rx = 0, tbs = 0;
+    for (int i = 0; i < n; ++i) {
+        const nrldpc_tb_params* q = p + i;
+        nrldpc::RmExArgs blocks;
+        const int rc = mix_check_cfg(q, n_tb[i], i, blocks);
+        if (rc) return rc;
+        const int pay = q->K_prime - q->cb_crc_len;
+        if (pay < q->tb_crc_len) return mix_fail_at(fail(NRLDPC_ERR_UNSUPPORTED, "code block shorter than the transport-block CRC"), i);
+        if (q->Q_m != 1 && q->Q_m != 2 && q->Q_m != 4 && q->Q_m != 6 && q->Q_m != 8) return mix_fail_at(fail(NRLDPC_ERR_UNSUPPORTED, "Unsupported modulation"), i);
+        const int32_t ncwz = 2 * q->Z + q->N;
+        int64_t s[nrldpc::MIX_FIELDS];
+        nrldpc::mix_sizes(n_tb[i], q->C, q->G, q->N_cb, ncwz, q->K, q->B, s);
+        const int64_t* cur = &m.off[i].g;
+        int64_t* next = &m.off[i + 1].g;
+        for (int k = 0; k < nrldpc::MIX_FIELDS; ++k) next[k] = nrldpc::mix_round_up(cur[k] + s[k]);
+        m.a_off[i + 1] = nrldpc::mix_tx_a_next(m.a_off[i], n_tb[i], q->A);
+        m.used_a += (int64_t)n_tb[i] * q->A; m.used_c += s[nrldpc::MIX_C_HAT]; m.used_cw += s[nrldpc::MIX_CW]; m.used_g += s[nrldpc::MIX_G];
+        int32_t e_max = 0;
+        for (int b = 0; b < q->C; ++b) e_max = std::max(e_max, blocks.E[b]);
+        const int32_t per = nrldpc::mix_tx_rm_wg_per_cb(e_max, q->Q_m);
+        wg += (int64_t)n_tb[i] * q->C * per;
+        wg_rx += (int64_t)n_tb[i] * q->C * nrldpc::mix_rm_wg_per_cb(ncwz); // (a plan nrldpc_mix_create refuses is refused here too)
+        tbs += n_tb[i];
+        if (wg > INT32_MAX || wg_rx > INT32_MAX || tbs > INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
+        m.rm_prefix[i + 1] = (int32_t)wg;
+        m.tb_prefix[i + 1] = (int32_t)tbs;
+        if (!tables) continue;
+        if (n_tb[i] > 0) { m.k_max = std::max(m.k_max, q->K); m.c_max = std::max(m.c_max, q->C); }
+        nrldpc::MixTxRmRec& r = m.rm[i];
+        memset(&r, 0, sizeof r);
+        r.cw_off = cur[nrldpc::MIX_CW]; r.g_off = cur[nrldpc::MIX_G];
+        r.n_tb = n_tb[i]; r.C = q->C; r.G = q->G; r.Z = q->Z; r.K = q->K; r.Kp = q->K_prime; r.N = q->N; r.N_cb = q->N_cb;
+        r.k0 = q->k_0; r.Qm = q->Q_m;
+        r.e_base = (int32_t)m.e_tab.size();
+        r.wg_per_cb = per;
+        for (int b = 0; b < q->C; ++b) { m.e_tab.push_back(blocks.E[b]); m.off_tab.push_back(blocks.off[b]); }
+        nrldpc::MixTxCrcRec& c = m.crc[i];
+        memset(&c, 0, sizeof c);
+        c.g.a_off = m.a_off[i]; c.g.c_off = cur[nrldpc::MIX_C_HAT];
+        c.g.C = q->C; c.g.K = q->K; c.g.Kp = q->K_prime; c.g.Lcb = q->cb_crc_len; c.g.A = q->A; c.g.B = q->B;
+        // the plans of nrldpc_crc_attach_dev, not of the receive side: horner_tail for the shorter last segment, the code-block plan
+        // over the payload K' - L_cb
+        make_crc_plan(&c.tb, crc_poly_for(q->tb_crc_len, false), q->tb_crc_len, pay, pay, pay - q->tb_crc_len);
+        make_crc_plan(&c.cb, crc_poly_for(24, true), 24, pay, 0, 0);
+    }
+    return NRLDPC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nrldpc_mix_tx_layout(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int64_t* a_off) {
+    NRLDPC_API_BEGIN
+    if (n >= 0 && !a_off) return fail(NRLDPC_ERR_ARG, "null array");
+    MixTxHost m;
+    int rc = mix_tx_build(n, p, n_tb, false, m);
+    if (rc) return rc;
+    memcpy(a_off, m.a_off.data(), m.a_off.size() * sizeof(int64_t));
+    return NRLDPC_OK;
+    NRLDPC_API_END
+}
+
+void nrldpc_mix_tx_destroy(nrldpc_mix_tx_handle m) {
+    if (!m) return;
+    if (m->blob) { DeviceScope scope(m->device_id); (void)hipFree(m->blob); }
+    delete m;
+}
+
+int nrldpc_mix_tx_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int32_t device_id, nrldpc_mix_tx_handle* out) {
+    NRLDPC_API_BEGIN
+    if (!out) return fail(NRLDPC_ERR_ARG, "null out");
+    *out = nullptr;
+    MixTxHost mh;
+    int rc = mix_tx_build(n, p, n_tb, true, mh);
+    if (rc) return rc;
+    const bool empty = n == 0 || mh.tb_prefix[n] == 0; // an empty plan: no tables, no launches, no device call at all
+    if (!empty) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+            return fail(NRLDPC_ERR_HIP, "no HIP device available (this library has no CPU path)");
+        if (device_id < 0 || device_id >= ndev) return fail(NRLDPC_ERR_ARG, "device_id out of range");
+    }
+    nrldpc_mix_tx* m = new (std::nothrow) nrldpc_mix_tx();
+    if (!m) return fail(NRLDPC_ERR_NOMEM, "host allocation failed");
+    m->n = n; m->device_id = device_id; m->off = mh.off; m->a_off = mh.a_off;
+    for (int i = 0; i < n; ++i) { m->bg.push_back(p[i].bg); m->Z.push_back(p[i].Z); m->n_cw.push_back(n_tb[i] * p[i].C); }
+    m->size_a = mh.used_a; m->size_c = mh.used_c; m->size_cw = mh.used_cw; m->size_g = mh.used_g;
+    m->rm.n = n; m->rm.n_wg = mh.rm_prefix[n];
+    m->crc.n = n; m->crc.n_tb_total = mh.tb_prefix[n];
+    m->crc.k_max = mh.k_max; m->crc.c_max = mh.c_max; m->crc.waves = nrldpc::mix_tx_waves(mh.c_max);
+    if (empty) { *out = m; return NRLDPC_OK; }
+    // one allocation, every table at a multiple of 16 bytes, uploaded synchronously and never written again
+    auto pad16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_rm = 0, o_crc = o_rm + pad16(mh.rm.size() * sizeof(nrldpc::MixTxRmRec)), o_rp = o_crc + pad16(mh.crc.size() * sizeof(nrldpc::MixTxCrcRec)),
+                 o_tp = o_rp + pad16(mh.rm_prefix.size() * 4), o_e = o_tp + pad16(mh.tb_prefix.size() * 4), o_o = o_e + pad16(mh.e_tab.size() * 4),
+                 total = o_o + pad16(mh.off_tab.size() * 4);
+    std::vector<char> img(total, 0);
+    memcpy(img.data() + o_rm, mh.rm.data(), mh.rm.size() * sizeof(nrldpc::MixTxRmRec));
+    memcpy(img.data() + o_crc, mh.crc.data(), mh.crc.size() * sizeof(nrldpc::MixTxCrcRec));
+    memcpy(img.data() + o_rp, mh.rm_prefix.data(), mh.rm_prefix.size() * 4);
+    memcpy(img.data() + o_tp, mh.tb_prefix.data(), mh.tb_prefix.size() * 4);
+    memcpy(img.data() + o_e, mh.e_tab.data(), mh.e_tab.size() * 4);
+    memcpy(img.data() + o_o, mh.off_tab.data(), mh.off_tab.size() * 4);
+    DeviceScope scope(device_id);
+    hipError_t e = scope.err;
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->blob), total);
+    if (e == hipSuccess) e = hipMemcpy(m->blob, img.data(), total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { nrldpc_mix_tx_destroy(m); return hipfail(e, "mix transmit plan tables"); }
+    m->rm.recs = reinterpret_cast<const nrldpc::MixTxRmRec*>(m->blob + o_rm);
+    m->crc.recs = reinterpret_cast<const nrldpc::MixTxCrcRec*>(m->blob + o_crc);
+    m->rm.prefix = reinterpret_cast<const int32_t*>(m->blob + o_rp);
+    m->crc.prefix = reinterpret_cast<const int32_t*>(m->blob + o_tp);
+    m->rm.e_tab = reinterpret_cast<const int32_t*>(m->blob + o_e);
+    m->rm.off_tab = reinterpret_cast<const int32_t*>(m->blob + o_o);
+    *out = m;
+    return NRLDPC_OK;
+    NRLDPC_API_END
+}
+
+int nrldpc_mix_tx_crc_attach_dev(nrldpc_mix_tx_handle m, const uint8_t* d_a, uint8_t* d_c, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if ((m->size_a > 0 && !d_a) || (m->size_c > 0 && !d_c)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->crc.n_tb_total == 0) return NRLDPC_OK;
+    nrldpc::MixTxCrcLaunch a = m->crc; // (a copy: calls in flight on several streams share the plan, never a launch block)
+    a.a = d_a; a.c = d_c;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_tx_crc_attach(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix CRC attach kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_tx_encode_dev(nrldpc_mix_tx_handle m, const nrldpc_handle* h, const uint8_t* d_c, uint8_t* d_cw, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if ((m->size_c > 0 && !d_c) || (m->size_cw > 0 && !d_cw)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->crc.n_tb_total == 0) return NRLDPC_OK;
+    if (!h) return fail(NRLDPC_ERR_ARG, "null array");
+    for (int i = 0; i < m->n; ++i) { // every handle checked before the first launch
+        if (m->n_cw[i] == 0) continue;
+        if (!h[i]) return mix_fail_at(fail(NRLDPC_ERR_ARG, "null handle"), i);
+        if (h[i]->cfg.bg != m->bg[i] || h[i]->cfg.Z != m->Z[i]) return mix_fail_at(fail(NRLDPC_ERR_ARG, "the handle's (BG, Z) is not the configuration's"), i);
+        if (h[i]->cfg.device_id != m->device_id) return mix_fail_at(fail(NRLDPC_ERR_ARG, "the handle lives on another device than the plan"), i);
+    }
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    for (int i = 0; i < m->n; ++i) {
+        if (m->n_cw[i] == 0) continue;
+        const int rc = encode_launch(h[i], d_c + m->off[i].c_hat, m->n_cw[i], d_cw + m->off[i].cw, static_cast<hipStream_t>(stream));
+        if (rc) return mix_fail_at(rc, i);
+    }
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_tx_rate_match_dev(nrldpc_mix_tx_handle m, const uint8_t* d_cw, uint8_t* d_g, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if ((m->size_cw > 0 && !d_cw) || (m->size_g > 0 && !d_g)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->rm.n_wg == 0) return NRLDPC_OK;
+    nrldpc::MixTxRmLaunch a = m->rm;
+    a.cw = d_cw; a.g = d_g;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_tx_rate_match(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix rate-matching kernel launch");
     return NRLDPC_OK;
 }
 

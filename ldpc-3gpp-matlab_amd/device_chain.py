@@ -8,7 +8,7 @@ import copy
 
 import numpy as np
 
-from ._capi import LLR_F16, LLR_F32, MIX_FIELDS, Codec, MixPlan, MultiCall, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
+from ._capi import LLR_F16, LLR_F32, MIX_FIELDS, Codec, MixPlan, MixTxPlan, MultiCall, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
 from .nrldpc import NRLDPC
 
 
@@ -411,3 +411,104 @@ class DeviceEncodeChain:
         g = torch.empty((n_tb, d.G), dtype=torch.uint8, device=self.dev)
         self._rate_match(t, cw.data_ptr(), n_tb, g.data_ptr(), s)
         return g
+
+
+class MixedEncodeChain:
+    """The transmit chain for a MIX of configurations, the twin of MixedDecodeChain: n parameter sets (NRLDPC objects) with n_tb[i]
+    transport blocks each, from payload bits to rate-matched bits -- mix CRC attach (one launch), the existing encoder once per
+    non-empty configuration, mix rate matching (one launch).  Every array is PACKED: configuration i's segment of the payload starts
+    at plan.a_off[i] bytes, its code blocks, codeword bytes and rate-matched bits at plan.off[i].c_hat / .cw / .g, and each segment
+    is exactly the array DeviceEncodeChain uses for that configuration; views() / pack() convert.  The packed g is the layout of
+    MixedDecodeChain's "g" field for the same (params, n_tb).  One Codec per distinct (BG, Z_c) among the non-empty configurations."""
+
+    _SHAPES = {"a": lambda t, n: (n, t.A), "c": lambda t, n: (n * t.C, t.K), "cw": lambda t, n: (n * t.C, 2 * t.Z + t.N), "g": lambda t, n: (n, t.G)}
+    _OFF = {"c": "c_hat", "cw": "cw", "g": "g"}
+
+    def __init__(self, params, n_tb, device_id=0):
+        import torch
+        self.torch = torch
+        params = list(params)
+        for p in params:
+            p.validate()
+        self.params, self.n_tb = params, [int(x) for x in n_tb]
+        self.dev = torch.device("cuda", device_id)
+        self.device_id = device_id
+        self._codecs = {}
+        self.codecs = []
+        self.c = self.cw = self.g = None
+        self.plan = MixTxPlan(params, self.n_tb, device_id=device_id)
+        try:
+            for p, k in zip(params, self.n_tb):
+                key = (p.BG, p.Z_c)
+                if k and key not in self._codecs:
+                    self._codecs[key] = Codec(p.BG, p.Z_c, max_iter=1, llr_dtype=np.float32, device_id=device_id)
+                self.codecs.append(self._codecs[key] if k else None)
+            tot = self.plan.totals()
+            if any(self.n_tb):
+                # the chain's own packed arrays, allocated once at the plan's totals (gaps stay zero: the kernels never touch them)
+                self.c = torch.zeros(tot["c"], dtype=torch.uint8, device=self.dev)
+                self.cw = torch.zeros(tot["cw"], dtype=torch.uint8, device=self.dev)
+                self.g = torch.zeros(tot["g"], dtype=torch.uint8, device=self.dev)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for c in getattr(self, "_codecs", {}).values():
+            c.close()
+        self._codecs, self.codecs = {}, []
+        if getattr(self, "plan", None) is not None:
+            self.plan.close()
+
+    def _offset(self, i, field):
+        return self.plan.a_off[i] if field == "a" else getattr(self.plan.off[i], self._OFF[field])
+
+    def views(self, packed, field):
+        """The per-configuration views of a packed tensor: field is one of "a", "c", "cw", "g"; view i has the shape of the
+        single-configuration array ([n_tb][A], [n_tb*C][K], [n_tb*C][N_cw], [n_tb][G])."""
+        if field not in self._SHAPES:
+            raise NRLDPCError("unknown field %r (one of %s)" % (field, ", ".join(self._SHAPES)))
+        flat = packed.reshape(-1)
+        if flat.numel() < self.plan.totals()[field]:
+            raise NRLDPCError("the packed %s array should hold at least %d elements." % (field, self.plan.totals()[field]))
+        out = []
+        for i, t in enumerate(self.plan.params):
+            shape = self._SHAPES[field](t, self.n_tb[i])
+            o = self._offset(i, field)
+            out.append(flat[o: o + int(np.prod(shape, dtype=np.int64))].view(shape))
+        return out
+
+    def pack(self, tensors, field):
+        """A packed uint8 tensor (gaps zero) from one tensor per configuration, each of the single-configuration shape for `field`."""
+        tensors = list(tensors)
+        if len(tensors) != len(self.params):
+            raise NRLDPCError("one tensor per configuration expected (%d), got %d." % (len(self.params), len(tensors)))
+        if field not in self._SHAPES:
+            raise NRLDPCError("unknown field %r (one of %s)" % (field, ", ".join(self._SHAPES)))
+        packed = self.torch.zeros(self.plan.totals()[field], dtype=self.torch.uint8, device=self.dev)
+        for v, x in zip(self.views(packed, field), tensors):
+            if tuple(x.shape) != tuple(v.shape) or x.dtype != self.torch.uint8:
+                raise NRLDPCError("a uint8 tensor of shape %s expected for field %r, got %s %s." % (tuple(v.shape), field, tuple(x.shape), x.dtype))
+            v.copy_(x)
+        return packed
+
+    def step(self, a_packed):
+        """a_packed: the packed payload bits, a contiguous 1-D uint8 device tensor of at least plan.totals()["a"] elements
+        (pack(..., "a")); only bit 0 of a byte is read.  Returns g_packed: the chain's own packed uint8 device array of rate-matched
+        bits, valid until the next step (clone what must live longer); views(g_packed, "g")[i] is configuration i's [n_tb][G]."""
+        torch, a = self.torch, a_packed
+        need = self.plan.totals()["a"]
+        if not isinstance(a, torch.Tensor) or a.dim() != 1 or a.dtype != torch.uint8 or not a.is_contiguous():
+            raise NRLDPCError("a should be a contiguous 1-D uint8 device tensor of at least %d elements." % need)
+        if not a.is_cuda or a.device != self.dev:
+            raise NRLDPCError("a lives on %s, this chain on %s." % (a.device, self.dev))
+        if a.numel() < need:
+            raise NRLDPCError("a should be a contiguous 1-D uint8 device tensor of at least %d elements, got %d." % (need, a.numel()))
+        if self.g is None:  # the empty plan: nothing to do
+            return torch.zeros(0, dtype=torch.uint8, device=self.dev)
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            self.plan.crc_attach(a.data_ptr(), self.c.data_ptr(), stream=stream)
+            self.plan.encode(self.codecs, self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
+            self.plan.rate_match(self.cw.data_ptr(), self.g.data_ptr() if self.g.numel() else None, stream=stream)
+        return self.g
