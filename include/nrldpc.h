@@ -520,6 +520,27 @@ int nrldpc_mix_tx_crc_attach_dev(nrldpc_mix_tx_handle m, const uint8_t* d_a, uin
 int nrldpc_mix_tx_encode_dev(nrldpc_mix_tx_handle m, const nrldpc_handle* h /* [n] */, const uint8_t* d_c, uint8_t* d_cw, void* stream);
 int nrldpc_mix_tx_rate_match_dev(nrldpc_mix_tx_handle m, const uint8_t* d_cw, uint8_t* d_g, void* stream);
 
+/* ---- the transmit plan's encode stage in ONE launch -------------------------------------------------------------------------------
+ * Added after the block above was written, again without a revision bump (a binding finds the function by symbol).  The
+ * per-configuration call nrldpc_mix_tx_encode_dev remains and behaves as described there; this call is the same stage with a kernel
+ * of its own, table driven like attach and rate matching, and takes no handle array: the base-graph tables and the solve order of
+ * every distinct (BG, Z_c) among the non-empty configurations are built by nrldpc_mix_tx_create and live in the plan's one device
+ * allocation, uploaded once and never written again -- streams may share a plan as before.
+ *
+ * Semantics, by equality.  nrldpc_mix_tx_encode_all_dev(m, c, cw, stream) leaves cw as nrldpc_mix_tx_encode_dev(m, h, c, cw, stream)
+ *   leaves it: in every segment what nrldpc_encode_dev(h[i], c + off[i].c_hat, n_tb[i]*C_i, cw + off[i].cw, stream) leaves, bit for
+ *   bit.  Only bit 0 of an input byte is read and every output byte is 0 or 1.  Gap bytes are never read or written; one thread
+ *   writes each output byte, no atomics.  Any byte address of the base pointers is served: every codeword takes, at its real
+ *   addresses, the copy, ring-build and store forms the single call takes there.  ONE launch whatever n; the call only enqueues.
+ *   Waves per codeword follow the single call's rule (four for BG1 from Z = 128 on, else one); the NRLDPC_ENC_NWC experiment knob is
+ *   not read.
+ *
+ * Refusals, before any device call: a null plan; a null base pointer whose array is not empty -> NRLDPC_ERR_ARG.  The empty plan
+ *   returns NRLDPC_OK without a launch and without a device.
+ *
+ * Which to call: DESIGN.md section 4.18 holds the measurement (a mix of many configurations against a uniform batch). */
+int nrldpc_mix_tx_encode_all_dev(nrldpc_mix_tx_handle m, const uint8_t* d_c, uint8_t* d_cw, void* stream);
+
 /* Channel leg of the Monte-Carlo loop, fused: replaces step(hMod,g), step(hChan,tx),
  * step(hDemod,rx) of plot_BLER_vs_SNR.m:130-132 -- NRModulator.m:73-81 (TS 38.211 maps, unit average power),
  * comm.AWGNChannel at EsN0_dB (:50,105), NRDemodulator.m:76-84 (exact LLRs, Variance = 10^(-EsN0/10), :106).

@@ -117,7 +117,7 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_mix_layout", "nrldpc_mix_create", "nrldpc_mix_destroy", "nrldpc_mix_rate_recover_dev", "nrldpc_mix_crc_check_dev",
            "nrldpc_mix_rate_recover_harq_dev", "nrldpc_mix_crc_check_harq_dev",
            "nrldpc_mix_tx_layout", "nrldpc_mix_tx_create", "nrldpc_mix_tx_destroy", "nrldpc_mix_tx_crc_attach_dev", "nrldpc_mix_tx_encode_dev",
-           "nrldpc_mix_tx_rate_match_dev"]
+           "nrldpc_mix_tx_rate_match_dev", "nrldpc_mix_tx_encode_all_dev"]
 
 _lib = None
 
@@ -211,6 +211,8 @@ def load():
         L.nrldpc_mix_tx_crc_attach_dev.argtypes = [vp, vp, vp, vp]
         L.nrldpc_mix_tx_encode_dev.argtypes = [vp, C.POINTER(vp), vp, vp, vp]
         L.nrldpc_mix_tx_rate_match_dev.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "nrldpc_mix_tx_encode_all_dev"):  # the encode stage in one launch, found by symbol like the rest
+        L.nrldpc_mix_tx_encode_all_dev.argtypes = [vp, vp, vp, vp]
     L.nrldpc_crc_attach_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_rate_match_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_pool_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), i32, i32, C.POINTER(vp)]
@@ -698,7 +700,8 @@ class MixTxPlan:
     (BG, A, G, Q_m, rv_id, LBRM, C).  .a_off: the n + 1 byte offsets of the packed payload array; .off: the receive layout's n + 1
     MixOffsets records, of which the transmit arrays use c_hat (code blocks), cw (codeword bytes) and g (rate-matched bits);
     totals(): {"a", "c", "cw", "g"} -> elements to allocate.  crc_attach() and rate_match() are one launch each, whatever n; encode()
-    launches the existing encoder once per non-empty configuration.  Streams may share a plan."""
+    launches the existing encoder once per non-empty configuration, encode_all() is the same stage in one launch from the plan's own
+    tables.  Streams may share a plan."""
 
     def __init__(self, params, n_tb, device_id=0):
         self._h = C.c_void_p()
@@ -732,6 +735,14 @@ class MixTxPlan:
             raise NRLDPCError("one codec per configuration expected (%d), got %d." % (self.n, len(codecs)))
         hs = (C.c_void_p * max(self.n, 1))(*[c._h if c is not None else None for c in codecs])
         check(self._lib.nrldpc_mix_tx_encode_dev(self._h, hs, _ptr(d_c), _ptr(d_cw), C.c_void_p(stream)))
+
+    def encode_all(self, d_c, d_cw, stream=0):
+        """nrldpc_mix_tx_encode_all_dev: the encode stage in ONE launch from the plan's own tables, no codecs; leaves cw as encode()
+        leaves it."""
+        if not hasattr(self._lib, "nrldpc_mix_tx_encode_all_dev"):
+            raise NRLDPCError("%s has no nrldpc_mix_tx_encode_all_dev: the one-launch mixed encoder needs a library built from this "
+                              "tree (NRLDPC_LIB selects an older one?)" % lib_path())
+        check(self._lib.nrldpc_mix_tx_encode_all_dev(self._h, _ptr(d_c), _ptr(d_cw), C.c_void_p(stream)))
 
     def rate_match(self, d_cw, d_g, stream=0):
         """nrldpc_mix_tx_rate_match_dev on raw device addresses of the packed arrays."""

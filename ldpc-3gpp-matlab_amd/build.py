@@ -29,7 +29,7 @@ NOPAIR = bool(os.environ.get("NRLDPC_BUILD_NOPAIR"))
 LIB = os.environ.get("NRLDPC_LIB") or os.path.join(HERE, "libnrldpc_hip_ab.so" if AB else "libnrldpc_hip_allmodes.so" if ALLMODES else "libnrldpc_hip_x.so" if XFLAGS else "libnrldpc_hip_nopair.so" if NOPAIR else "libnrldpc_hip.so")  # env override: kernel experiments
 OBJDIR = os.path.join(HERE, "build_ab" if AB else "build_allmodes" if ALLMODES else "build_x" if XFLAGS else "build_nopair" if NOPAIR else "build")
 SOURCES = ["nrldpc_decode.hip", "nrldpc_encode.hip", "nrldpc_ratematch.hip", "nrldpc_crc.hip", "nrldpc_channel.hip",
-           "nrldpc_expand.hip", "nrldpc_decode_bp.hip", "nrldpc_cwout.hip", "nrldpc_modem.hip", "nrldpc_awgn.hip", "nrldpc_ratematch_ex.hip", "nrldpc_mix.hip", "nrldpc_mix_tx.hip", "nrldpc_capi.hip", "nrldpc_host_quant.cpp"]  # .cpp: host-only C++ (no device pass)
+           "nrldpc_expand.hip", "nrldpc_decode_bp.hip", "nrldpc_cwout.hip", "nrldpc_modem.hip", "nrldpc_awgn.hip", "nrldpc_ratematch_ex.hip", "nrldpc_mix.hip", "nrldpc_mix_tx.hip", "nrldpc_mix_tx_enc.hip", "nrldpc_capi.hip", "nrldpc_host_quant.cpp"]  # .cpp: host-only C++ (no device pass)
 Z64_SOURCE = "nrldpc_decode_z64_inst.hip"
 Z64P_SOURCE = "nrldpc_decode_z64p_inst.hip"
 # the same instantiation with the split form's two-smallest search over pairs of edges (nrldpc_decode_z64_pair.h)

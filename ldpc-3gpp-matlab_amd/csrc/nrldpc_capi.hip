@@ -450,14 +450,14 @@ size_t llr_elem_bytes(int dtype) { return dtype == NRLDPC_LLR_F16 ? 2 : 4; }
 
 // Substitution order for the core-parity blocks (same derivation as the oracle's encode_one, from the
 // dual-diagonal entries at get_3gpp_base_graph.m:30-31,48-50,68-69,87-88 / :339-340,349-350,356-358,367-368).
-bool derive_encoder_order(nrldpc_codec* h) {
-    const nrldpc::Schedule& s = h->sched;
-    const nrldpc::BaseGraph& g = s.g;
+// `shift`: the table's shifts reduced mod Z, per base-graph edge.  Fills *o (zeroed first: entries past step_nk stay 0).
+bool derive_encoder_order(const nrldpc::BaseGraph& g, const int32_t* shift, nrldpc::EncSolveOrder* o) {
+    *o = nrldpc::EncSolveOrder{};
     const int kb = g.kb;
     int cnt[4] = {0, 0, 0, 0}, sh0[4] = {0, 0, 0, 0};
     for (int i = 0; i < 4; ++i)
         for (int e = g.row_ptr[i]; e < g.row_ptr[i + 1]; ++e)
-            if (g.col[e] == kb) { cnt[i] = 1; sh0[i] = s.shift[e]; }
+            if (g.col[e] == kb) { cnt[i] = 1; sh0[i] = shift[e]; }
     int a = -1;
     for (int i = 0; i < 4; ++i) {
         if (!cnt[i]) continue;
@@ -466,7 +466,7 @@ bool derive_encoder_order(nrldpc_codec* h) {
         if (n & 1) a = sh0[i];
     }
     if (a < 0) return false;
-    h->p0_shift = a;
+    o->p0_shift = a;
     bool known[4] = {true, false, false, false};
     for (int st = 0; st < 3; ++st) {
         bool found = false;
@@ -474,23 +474,36 @@ bool derive_encoder_order(nrldpc_codec* h) {
             int unk = -1, nunk = 0, ush = 0;
             for (int e = g.row_ptr[i]; e < g.row_ptr[i + 1]; ++e) {
                 int c = g.col[e] - kb;
-                if (c >= 0 && c < 4 && !known[c]) { unk = c; ush = s.shift[e]; ++nunk; }
+                if (c >= 0 && c < 4 && !known[c]) { unk = c; ush = shift[e]; ++nunk; }
             }
             if (nunk == 1) {
-                h->step_row[st] = i; h->step_col[st] = unk; h->step_shift[st] = ush;
+                o->step_row[st] = i; o->step_col[st] = unk; o->step_shift[st] = ush;
                 int nk = 0;
                 for (int e = g.row_ptr[i]; e < g.row_ptr[i + 1]; ++e) {
                     const int c = g.col[e] - kb;
                     if (c >= 0 && c < 4 && c != unk) {
                         if (nk == 3) return false;
-                        h->step_kcol[st][nk] = c; h->step_kshift[st][nk] = s.shift[e]; ++nk;
+                        o->step_kcol[st][nk] = c; o->step_kshift[st][nk] = shift[e]; ++nk;
                     }
                 }
-                h->step_nk[st] = nk;
+                o->step_nk[st] = nk;
                 known[unk] = true; found = true;
             }
         }
         if (!found) return false;
+    }
+    return true;
+}
+
+// the handle's copy of the same values
+bool derive_encoder_order(nrldpc_codec* h) {
+    nrldpc::EncSolveOrder o;
+    if (!derive_encoder_order(h->sched.g, h->sched.shift.data(), &o)) return false;
+    h->p0_shift = o.p0_shift;
+    for (int st = 0; st < 3; ++st) {
+        h->step_row[st] = o.step_row[st]; h->step_col[st] = o.step_col[st]; h->step_shift[st] = o.step_shift[st];
+        h->step_nk[st] = o.step_nk[st];
+        for (int k = 0; k < 3; ++k) { h->step_kcol[st][k] = o.step_kcol[st][k]; h->step_kshift[st][k] = o.step_kshift[st][k]; }
     }
     return true;
 }
@@ -2390,6 +2403,7 @@ struct nrldpc_mix_tx {
     char* blob = nullptr;                // every device table, one allocation, written once by nrldpc_mix_tx_create
     nrldpc::MixTxCrcLaunch crc{};
     nrldpc::MixTxRmLaunch rm{};
+    nrldpc::MixTxEncLaunch enc{};        // nrldpc_mix_tx_encode_all_dev
 };
 
 namespace {
@@ -2402,7 +2416,46 @@ struct MixTxHost {
     std::vector<int32_t> rm_prefix, tb_prefix, e_tab, off_tab;
     int64_t used_a = 0, used_c = 0, used_cw = 0, used_g = 0;
     int32_t k_max = 0, c_max = 0;
+    // the one-launch encoder: records, workgroup prefix, the base-graph tables of every distinct (BG, Z_c), the launch's LDS size
+    std::vector<nrldpc::MixTxEncRec> enc;
+    std::vector<int32_t> enc_prefix, enc_first; // enc_first: the first configuration of each distinct (BG, Z_c)
+    std::vector<uint8_t> enc_tab;
+    int64_t enc_lds = 0;
 };
+
+// the encoder record of one non-empty configuration: sizes, waves per codeword, and -- once per distinct (BG, Z_c) -- the solve order
+// and the tables EncArgs points to (row_ptr, col, shift reduced mod Z) appended to m.enc_tab
+int mix_tx_enc_fill(int32_t bg, int32_t Z, int32_t i, MixTxHost& m) {
+    nrldpc::MixTxEncRec& en = m.enc[i];
+    nrldpc::BaseGraph g;
+    const int ils = nrldpc::set_index(Z);
+    if (!nrldpc::base_graph(bg, &g) || ils < 0) return fail(NRLDPC_ERR_UNSUPPORTED, "invalid BG / lifting size");
+    en.Z = Z; en.kb = g.kb; en.nrows = g.nrows; en.ncols = g.ncols; en.nnz = g.nnz;
+    en.nwc = nrldpc::mix_tx_enc_nwc(bg, Z);
+    const int64_t lds = nrldpc::mix_tx_enc_lds_bytes(nrldpc::mix_tx_enc_layout(Z, g.kb, g.nrows, g.nnz), en.nwc);
+    if (lds > 64 * 1024) return fail(NRLDPC_ERR_UNSUPPORTED, "the encoder's LDS does not fit a workgroup");
+    m.enc_lds = std::max(m.enc_lds, lds);
+    for (int32_t k : m.enc_first) {
+        const nrldpc::MixTxEncRec& f = m.enc[k];
+        if (f.kb == en.kb && f.Z == Z) { // the same (BG, Z_c): one table, one solve order
+            en.row_ptr_off = f.row_ptr_off; en.shift_off = f.shift_off; en.col_off = f.col_off; en.ord = f.ord;
+            return NRLDPC_OK;
+        }
+    }
+    std::vector<int32_t> shift((size_t)g.nnz);
+    for (int e = 0; e < g.nnz; ++e) shift[(size_t)e] = g.raw_shift(ils, e) % Z;
+    if (!derive_encoder_order(g, shift.data(), &en.ord)) return fail(NRLDPC_ERR_UNSUPPORTED, "base graph core is not dual-diagonal");
+    const size_t base = m.enc_tab.size();
+    if (base + (size_t)nrldpc::mix_tx_enc_tab_bytes(g.nrows, g.nnz) > (size_t)INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
+    nrldpc::mix_tx_enc_tab_place((int32_t)base, en);
+    m.enc_tab.resize(base + (size_t)nrldpc::mix_tx_enc_tab_bytes(g.nrows, g.nnz), 0);
+    memcpy(m.enc_tab.data() + en.row_ptr_off, g.row_ptr, (size_t)(g.nrows + 1) * 2);
+    std::vector<uint16_t> sh16(shift.begin(), shift.end());
+    memcpy(m.enc_tab.data() + en.shift_off, sh16.data(), (size_t)g.nnz * 2);
+    memcpy(m.enc_tab.data() + en.col_off, g.col, (size_t)g.nnz);
+    m.enc_first.push_back(i);
+    return NRLDPC_OK;
+}
 
 // everything the transmit plan needs, on the host.  No device call.  The refusals of mix_build, then the transmit stages' own.
 int mix_tx_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool tables, MixTxHost& m) {
@@ -2412,8 +2465,9 @@ int mix_tx_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool
     m.a_off.assign((size_t)n + 1, 0);
     m.rm_prefix.assign((size_t)n + 1, 0);
     m.tb_prefix.assign((size_t)n + 1, 0);
-    if (tables) { m.rm.resize(n); m.crc.resize(n); }
-    int64_t wg = 0, wg_rx = 0, tbs = 0;
+    m.enc_prefix.assign((size_t)n + 1, 0);
+    if (tables) { m.rm.resize(n); m.crc.resize(n); m.enc.resize(n); }
+    int64_t wg = 0, wg_rx = 0, tbs = 0, wg_enc = 0;
     for (int i = 0; i < n; ++i) {
         const nrldpc_tb_params* q = p + i;
         nrldpc::RmExArgs blocks;
@@ -2436,9 +2490,13 @@ int mix_tx_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool
         wg += (int64_t)n_tb[i] * q->C * per;
         wg_rx += (int64_t)n_tb[i] * q->C * nrldpc::mix_rm_wg_per_cb(ncwz); // (a plan nrldpc_mix_create refuses is refused here too)
         tbs += n_tb[i];
-        if (wg > INT32_MAX || wg_rx > INT32_MAX || tbs > INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
+        const int64_t n_cw = (int64_t)n_tb[i] * q->C; // (below 2^31 once wg_rx is: a code block takes a receive workgroup at least)
+        const int32_t nwc = nrldpc::mix_tx_enc_nwc(q->bg, q->Z), per_enc = nrldpc::mix_tx_enc_per_wg(nwc);
+        wg_enc += (n_cw + per_enc - 1) / per_enc;
+        if (wg > INT32_MAX || wg_rx > INT32_MAX || tbs > INT32_MAX || wg_enc > INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
         m.rm_prefix[i + 1] = (int32_t)wg;
         m.tb_prefix[i + 1] = (int32_t)tbs;
+        m.enc_prefix[i + 1] = (int32_t)wg_enc;
         if (!tables) continue;
         if (n_tb[i] > 0) { m.k_max = std::max(m.k_max, q->K); m.c_max = std::max(m.c_max, q->C); }
         nrldpc::MixTxRmRec& r = m.rm[i];
@@ -2457,6 +2515,14 @@ int mix_tx_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool
         // over the payload K' - L_cb
         make_crc_plan(&c.tb, crc_poly_for(q->tb_crc_len, false), q->tb_crc_len, pay, pay, pay - q->tb_crc_len);
         make_crc_plan(&c.cb, crc_poly_for(24, true), 24, pay, 0, 0);
+        nrldpc::MixTxEncRec& en = m.enc[i];
+        memset(&en, 0, sizeof en);
+        en.c_off = cur[nrldpc::MIX_C_HAT]; en.cw_off = cur[nrldpc::MIX_CW];
+        en.n_cw = (int32_t)n_cw;
+        if (n_cw > 0) { // (an empty configuration has no workgroup: its record is never read)
+            const int rce = mix_tx_enc_fill(q->bg, q->Z, i, m);
+            if (rce) return mix_fail_at(rce, i);
+        }
     }
     return NRLDPC_OK;
 }
@@ -2504,12 +2570,14 @@ int nrldpc_mix_tx_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_
     m->rm.n = n; m->rm.n_wg = mh.rm_prefix[n];
     m->crc.n = n; m->crc.n_tb_total = mh.tb_prefix[n];
     m->crc.k_max = mh.k_max; m->crc.c_max = mh.c_max; m->crc.waves = nrldpc::mix_tx_waves(mh.c_max);
+    m->enc.n = n; m->enc.n_wg = mh.enc_prefix[n]; m->enc.lds_bytes = (int32_t)mh.enc_lds;
     if (empty) { *out = m; return NRLDPC_OK; }
     // one allocation, every table at a multiple of 16 bytes, uploaded synchronously and never written again
     auto pad16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_rm = 0, o_crc = o_rm + pad16(mh.rm.size() * sizeof(nrldpc::MixTxRmRec)), o_rp = o_crc + pad16(mh.crc.size() * sizeof(nrldpc::MixTxCrcRec)),
                  o_tp = o_rp + pad16(mh.rm_prefix.size() * 4), o_e = o_tp + pad16(mh.tb_prefix.size() * 4), o_o = o_e + pad16(mh.e_tab.size() * 4),
-                 total = o_o + pad16(mh.off_tab.size() * 4);
+                 o_er = o_o + pad16(mh.off_tab.size() * 4), o_ep = o_er + pad16(mh.enc.size() * sizeof(nrldpc::MixTxEncRec)),
+                 o_et = o_ep + pad16(mh.enc_prefix.size() * 4), total = o_et + pad16(mh.enc_tab.size());
     std::vector<char> img(total, 0);
     memcpy(img.data() + o_rm, mh.rm.data(), mh.rm.size() * sizeof(nrldpc::MixTxRmRec));
     memcpy(img.data() + o_crc, mh.crc.data(), mh.crc.size() * sizeof(nrldpc::MixTxCrcRec));
@@ -2517,6 +2585,9 @@ int nrldpc_mix_tx_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_
     memcpy(img.data() + o_tp, mh.tb_prefix.data(), mh.tb_prefix.size() * 4);
     memcpy(img.data() + o_e, mh.e_tab.data(), mh.e_tab.size() * 4);
     memcpy(img.data() + o_o, mh.off_tab.data(), mh.off_tab.size() * 4);
+    memcpy(img.data() + o_er, mh.enc.data(), mh.enc.size() * sizeof(nrldpc::MixTxEncRec));
+    memcpy(img.data() + o_ep, mh.enc_prefix.data(), mh.enc_prefix.size() * 4);
+    memcpy(img.data() + o_et, mh.enc_tab.data(), mh.enc_tab.size());
     DeviceScope scope(device_id);
     hipError_t e = scope.err;
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->blob), total);
@@ -2528,6 +2599,9 @@ int nrldpc_mix_tx_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_
     m->crc.prefix = reinterpret_cast<const int32_t*>(m->blob + o_tp);
     m->rm.e_tab = reinterpret_cast<const int32_t*>(m->blob + o_e);
     m->rm.off_tab = reinterpret_cast<const int32_t*>(m->blob + o_o);
+    m->enc.recs = reinterpret_cast<const nrldpc::MixTxEncRec*>(m->blob + o_er);
+    m->enc.prefix = reinterpret_cast<const int32_t*>(m->blob + o_ep);
+    m->enc.tab = reinterpret_cast<const uint8_t*>(m->blob + o_et);
     *out = m;
     return NRLDPC_OK;
     NRLDPC_API_END
@@ -2564,6 +2638,20 @@ int nrldpc_mix_tx_encode_dev(nrldpc_mix_tx_handle m, const nrldpc_handle* h, con
         const int rc = encode_launch(h[i], d_c + m->off[i].c_hat, m->n_cw[i], d_cw + m->off[i].cw, static_cast<hipStream_t>(stream));
         if (rc) return mix_fail_at(rc, i);
     }
+    return NRLDPC_OK;
+}
+
+// the encode stage in one launch (nrldpc_mix_tx_enc.hip): no handles, the plan's own tables
+int nrldpc_mix_tx_encode_all_dev(nrldpc_mix_tx_handle m, const uint8_t* d_c, uint8_t* d_cw, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if ((m->size_c > 0 && !d_c) || (m->size_cw > 0 && !d_cw)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->enc.n_wg == 0) return NRLDPC_OK;
+    nrldpc::MixTxEncLaunch a = m->enc; // (a copy: calls in flight on several streams share the plan, never a launch block)
+    a.c = d_c; a.cw = d_cw;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_tx_encode(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix encode kernel launch");
     return NRLDPC_OK;
 }
 

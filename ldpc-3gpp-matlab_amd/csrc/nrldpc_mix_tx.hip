@@ -1,7 +1,7 @@
 // nrldpc_mix_tx.hip -- CRC attach and rate matching for a MIX of transport-block configurations in one launch each
 // (nrldpc_mix_tx_crc_attach_dev, nrldpc_mix_tx_rate_match_dev; semantics: include/nrldpc.h): the transmit mirror
 // of nrldpc_mix.hip.  The encoder between them is not here: nrldpc_mix_tx_encode_dev launches the existing kernel once per
-// configuration at the plan's offsets.
+// configuration at the plan's offsets, and the one-launch form nrldpc_mix_tx_encode_all_dev has a unit of its own (nrldpc_mix_tx_enc.hip).
 //
 // Both kernels are table driven, like the receive side's.  The per-configuration records (sizes, E_r and its offsets, the two CRC
 // plans) and a prefix table over the work items live in device memory, uploaded once by nrldpc_mix_tx_create and never written

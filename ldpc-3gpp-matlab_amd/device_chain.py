@@ -419,12 +419,14 @@ class MixedEncodeChain:
     non-empty configuration, mix rate matching (one launch).  Every array is PACKED: configuration i's segment of the payload starts
     at plan.a_off[i] bytes, its code blocks, codeword bytes and rate-matched bits at plan.off[i].c_hat / .cw / .g, and each segment
     is exactly the array DeviceEncodeChain uses for that configuration; views() / pack() convert.  The packed g is the layout of
-    MixedDecodeChain's "g" field for the same (params, n_tb).  One Codec per distinct (BG, Z_c) among the non-empty configurations."""
+    MixedDecodeChain's "g" field for the same (params, n_tb).  One Codec per distinct (BG, Z_c) among the non-empty configurations.
+    one_launch_encode=True: the encode stage is MixTxPlan.encode_all -- one launch from the plan's own tables -- and the chain builds
+    no Codec; the result is the same bit for bit.  The default stays the per-configuration loop."""
 
     _SHAPES = {"a": lambda t, n: (n, t.A), "c": lambda t, n: (n * t.C, t.K), "cw": lambda t, n: (n * t.C, 2 * t.Z + t.N), "g": lambda t, n: (n, t.G)}
     _OFF = {"c": "c_hat", "cw": "cw", "g": "g"}
 
-    def __init__(self, params, n_tb, device_id=0):
+    def __init__(self, params, n_tb, device_id=0, one_launch_encode=False):
         import torch
         self.torch = torch
         params = list(params)
@@ -433,6 +435,7 @@ class MixedEncodeChain:
         self.params, self.n_tb = params, [int(x) for x in n_tb]
         self.dev = torch.device("cuda", device_id)
         self.device_id = device_id
+        self.one_launch_encode = bool(one_launch_encode)
         self._codecs = {}
         self.codecs = []
         self.c = self.cw = self.g = None
@@ -440,9 +443,9 @@ class MixedEncodeChain:
         try:
             for p, k in zip(params, self.n_tb):
                 key = (p.BG, p.Z_c)
-                if k and key not in self._codecs:
+                if k and not self.one_launch_encode and key not in self._codecs:
                     self._codecs[key] = Codec(p.BG, p.Z_c, max_iter=1, llr_dtype=np.float32, device_id=device_id)
-                self.codecs.append(self._codecs[key] if k else None)
+                self.codecs.append(self._codecs[key] if k and not self.one_launch_encode else None)
             tot = self.plan.totals()
             if any(self.n_tb):
                 # the chain's own packed arrays, allocated once at the plan's totals (gaps stay zero: the kernels never touch them)
@@ -509,6 +512,9 @@ class MixedEncodeChain:
         with torch.cuda.device(self.dev):
             stream = torch.cuda.current_stream(self.dev).cuda_stream
             self.plan.crc_attach(a.data_ptr(), self.c.data_ptr(), stream=stream)
-            self.plan.encode(self.codecs, self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
+            if self.one_launch_encode:
+                self.plan.encode_all(self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
+            else:
+                self.plan.encode(self.codecs, self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
             self.plan.rate_match(self.cw.data_ptr(), self.g.data_ptr() if self.g.numel() else None, stream=stream)
         return self.g
