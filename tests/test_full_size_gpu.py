@@ -124,8 +124,8 @@ def test_host_and_device_entry_points_agree(pkg, orc):
 @pytest.mark.parametrize("dt,B,bg,Z", [(np.float64, 1237, 1, 384), (np.float32, 1001, 1, 384), (np.float16, 2049, 1, 384),
                                         (np.float32, 9001, 2, 20), (np.float64, 3001, 1, 36)])  # ... and two run-time-Z sizes
 def test_pipelined_host_path_equals_one_device_launch(pkg, orc, dt, B, bg, Z):
-    """Batches above 32 MB take the chunked, double-buffered host path of nrldpc_decode (pinned staging, copy
-    threads, two streams); it must return exactly what one device launch on the same LLRs returns, for a
+    """Batches of 8 MiB of device-format input and more take the chunked host path of nrldpc_decode (pinned staging slots,
+    copy threads, two streams); it must return exactly what one device launch on the same LLRs returns, for a
     batch that is not a multiple of the chunk size and for every boundary dtype (MATLAB doubles included)."""
     import torch
     rng = np.random.default_rng(B)
