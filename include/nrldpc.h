@@ -464,6 +464,58 @@ int nrldpc_mix_crc_check_harq_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, u
                                   int32_t* d_cb_pass /* required, in/out */, const uint8_t* d_cbgti /* nullable */,
                                   const uint8_t* d_new /* nullable */, void* stream);
 
+/* ---- mixed HARQ steps that decode only the code blocks still pending -------------------------------------------------------------
+ * Between nrldpc_mix_rate_recover_harq_dev and nrldpc_mix_crc_check_harq_dev the decoder decodes every code block of every transport
+ * block, also those whose hard decisions the CRC stage then throws away (CBGTI flag 0, NRLDPCDecoder.m:304) and those acknowledged
+ * rounds ago.  These three calls turn the HARQ state into a DENSE batch and back: nrldpc_mix_pending_dev compacts the pending code
+ * blocks of every configuration into an index list and a count, nrldpc_mix_gather_cw_dev copies their LLR rows to the front of each
+ * configuration's segment of a second packed array, nrldpc_decode_multi_dev decodes batch[i] = count[i] rows there (it accepts
+ * batch[i] == 0), and nrldpc_mix_scatter_hard_dev puts the hard decisions back at their rows.  Added without a revision bump
+ * (NRLDPC_ABI_VERSION stays 6): a binding finds the functions by symbol.  The plain and HARQ stage calls above are unchanged.
+ *
+ * The rule.  For code block r of transport block tb of configuration i (packed index cb = off[i].cb + tb*C + r) let
+ *   f = d_cbgti ? d_cbgti[cb] != 0 : 1      w = d_new ? d_new[off[i].tb + tb] != 0 : 0
+ *   p = d_cb_pass[cb] != 0                  o = d_ok[off[i].tb + tb] != 0          allp = all C blocks of the transport block have p
+ * NRLDPC_MIX_SKIP_UNSCHEDULED: pending = f.  Reads neither d_cb_pass nor d_ok.  The CRC stage never takes a block with f = 0 over, so
+ *   b_hat, ok and cb_pass of a step are bit for bit what the step that decodes everything leaves, always.
+ * NRLDPC_MIX_SKIP_SETTLED: pending = f && (w || (!o && (C == 1 || !p || allp))): a scheduled block is decoded when its transport block
+ *   starts a new process; otherwise when the transport block is not yet acknowledged and the block is its only one (C == 1: there is
+ *   no code-block CRC, cb_pass says nothing), or has not passed, or all blocks passed and the transport-block CRC still fails (the
+ *   whole transport block is decoded again).  d_ok is the PREVIOUS step's ok array: that makes it state, zero after a reset.
+ *   DEVIATION from the reference: a settled block keeps the hard decisions of the step in which it settled (its row of d_c_hat) instead
+ *   of being decoded again on the combined buffer.  The two differ only when the re-decode would pass its CRC with other bits, or,
+ *   for C == 1, when the re-decode of an acknowledged block would fail.
+ *
+ * nrldpc_mix_pending_dev: d_index[off[i].cb + j], j < d_count[i], is the local row tb*C + r of the j-th pending block of configuration
+ *   i, in ascending order; entries from d_count[i] on and gap elements are not written; d_count has n entries.
+ * Dense arrays use the SAME packed layout and totals as the full ones: configuration i's dense rows start at off[i].cw / .c_hat / .cb and
+ *   there are d_count[i] of them, so the base pointers given to nrldpc_decode_multi_dev do not depend on the counts.
+ * nrldpc_mix_gather_cw_dev: dense row j of configuration i = row d_index[off[i].cb + j] of d_cw_llr, bit for bit (f32 or f16; NaN
+ *   payloads, infinities and -0.0 survive); dense rows from d_count[i] on are not written, the source is not written.
+ * nrldpc_mix_scatter_hard_dev: row d_index[off[i].cb + j] of d_c_hat = dense row j (K bytes).  Rows of blocks that are not pending are
+ *   NOT written: d_c_hat is in/out and keeps their earlier decisions.  With d_iters: the count of a block that is not pending
+ *   becomes 0, that of a pending block is d_iters_dense's (left as it is when d_iters_dense is null).
+ * All three: the counts are read on the device; one launch per call whatever n, enqueue only (no allocation, copy or
+ *   synchronisation); one writer per position, no atomics; results independent of how a mix is split into plans; gap elements never
+ *   read or written; the plan stays immutable and shareable between streams.  d_index and d_count must be what nrldpc_mix_pending_dev
+ *   left for the same plan (an index outside its configuration is not followed).
+ * Refusals, before any device call: a rule other than the two -> NRLDPC_ERR_UNSUPPORTED; a dtype other than F32 / F16 ->
+ *   NRLDPC_ERR_UNSUPPORTED; a null pointer of a required array of a non-empty plan -> NRLDPC_ERR_ARG (SETTLED requires d_cb_pass and
+ *   d_ok); on a plan without transport blocks all three return NRLDPC_OK without a launch and write nothing, d_count included.
+ * Out of scope: pool variants, the MEX gateway, the single-configuration chain (a plan with n = 1 serves it), rate recovery writing
+ *   dense rows directly (it would save the gather, but changes an existing kernel). */
+#define NRLDPC_MIX_SKIP_UNSCHEDULED 1
+#define NRLDPC_MIX_SKIP_SETTLED 2
+int nrldpc_mix_pending_dev(nrldpc_mix_handle m, int32_t rule,
+                           const int32_t* d_cb_pass, const int32_t* d_ok, /* SETTLED: required; UNSCHEDULED: not read */
+                           const uint8_t* d_cbgti /* nullable */, const uint8_t* d_new /* nullable */,
+                           int32_t* d_index /* packed cb layout */, int32_t* d_count /* [n] */, void* stream);
+int nrldpc_mix_gather_cw_dev(nrldpc_mix_handle m, const void* d_cw_llr, int32_t dtype,
+                             const int32_t* d_index, const int32_t* d_count, void* d_cw_dense, void* stream);
+int nrldpc_mix_scatter_hard_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat_dense, const int32_t* d_iters_dense /* nullable */,
+                                const int32_t* d_index, const int32_t* d_count,
+                                uint8_t* d_c_hat /* in/out */, int32_t* d_iters /* nullable */, void* stream);
+
 /* Transmit-side counterparts (vector generation for the Monte-Carlo harness, plot_BLER_vs_SNR.m:129):
  * nrldpc_crc_attach_dev replaces crc_calculation + code_block_segmentation of the encoder
  * (NRLDPCEncoder.m:70-124): d_a [n_tb][A] bits -> d_c [n_tb*C][K] code blocks (fillers 0), ready for

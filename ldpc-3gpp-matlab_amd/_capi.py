@@ -12,6 +12,7 @@ from . import build as _build
 
 OK, ERR_UNSUPPORTED, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, 1, 2, 3, 4
 LLR_F32, LLR_F16, LLR_F64 = 0, 1, 2
+MIX_SKIP_UNSCHEDULED, MIX_SKIP_SETTLED = 1, 2  # NRLDPC_MIX_SKIP_* of include/nrldpc.h
 
 
 class UnsupportedParameters(ValueError):
@@ -116,6 +117,7 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_modulate_dev", "nrldpc_demodulate_dev", "nrldpc_rate_recover_ex_dev", "nrldpc_awgn_dev",
            "nrldpc_mix_layout", "nrldpc_mix_create", "nrldpc_mix_destroy", "nrldpc_mix_rate_recover_dev", "nrldpc_mix_crc_check_dev",
            "nrldpc_mix_rate_recover_harq_dev", "nrldpc_mix_crc_check_harq_dev",
+           "nrldpc_mix_pending_dev", "nrldpc_mix_gather_cw_dev", "nrldpc_mix_scatter_hard_dev",
            "nrldpc_mix_tx_layout", "nrldpc_mix_tx_create", "nrldpc_mix_tx_destroy", "nrldpc_mix_tx_crc_attach_dev", "nrldpc_mix_tx_encode_dev",
            "nrldpc_mix_tx_rate_match_dev", "nrldpc_mix_tx_encode_all_dev"]
 
@@ -203,6 +205,10 @@ def load():
     if hasattr(L, "nrldpc_mix_rate_recover_harq_dev"):  # the HARQ / CBGTI forms, again without a revision bump
         L.nrldpc_mix_rate_recover_harq_dev.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp]
         L.nrldpc_mix_crc_check_harq_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "nrldpc_mix_pending_dev"):  # HARQ steps that decode only the pending code blocks, again without a revision bump
+        L.nrldpc_mix_pending_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.nrldpc_mix_gather_cw_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+        L.nrldpc_mix_scatter_hard_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "nrldpc_mix_tx_create"):  # the transmit side of the mixed batches, again without a revision bump
         L.nrldpc_mix_tx_layout.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), C.POINTER(C.c_int64)]
         L.nrldpc_mix_tx_create.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), i32, C.POINTER(vp)]
@@ -665,6 +671,33 @@ class MixPlan:
         block in the packed cb layout; None: all 1) and d_new as in rate_recover_harq."""
         check(self._harq_fn("nrldpc_mix_crc_check_harq_dev")(self._h, _ptr(d_c_hat), _ptr(d_b_hat), _ptr(d_ok), _ptr(d_cb_pass),
                                                              _ptr(d_cbgti), _ptr(d_new), C.c_void_p(stream)))
+
+    def _skip_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise NRLDPCError("%s has no %s: HARQ steps that decode only the pending code blocks need a library built from this "
+                              "tree (NRLDPC_LIB selects an older one?)" % (lib_path(), name))
+        return fn
+
+    def pending(self, rule, d_cb_pass, d_ok, d_cbgti, d_new, d_index, d_count, stream=0):
+        """nrldpc_mix_pending_dev on raw device addresses: rule = MIX_SKIP_UNSCHEDULED (d_cb_pass and d_ok are not read) or
+        MIX_SKIP_SETTLED (both required; d_ok is the previous step's ok array); d_cbgti / d_new as in crc_check_harq, nullable.
+        Leaves in d_index (int32, packed cb layout) the local rows of each configuration's pending code blocks, ascending, and in
+        d_count (int32 [n]) how many there are."""
+        check(self._skip_fn("nrldpc_mix_pending_dev")(self._h, int(rule), _ptr(d_cb_pass), _ptr(d_ok), _ptr(d_cbgti), _ptr(d_new),
+                                                      _ptr(d_index), _ptr(d_count), C.c_void_p(stream)))
+
+    def gather_cw(self, d_cw_llr, d_index, d_count, d_cw_dense, dtype=LLR_F32, stream=0):
+        """nrldpc_mix_gather_cw_dev on raw device addresses: dense row j of configuration i = row d_index[off[i].cb + j] of the packed
+        codeword LLRs, bit for bit, for j < d_count[i]; the dense array has the layout and size of the full one."""
+        check(self._skip_fn("nrldpc_mix_gather_cw_dev")(self._h, _ptr(d_cw_llr), int(dtype), _ptr(d_index), _ptr(d_count), _ptr(d_cw_dense),
+                                                        C.c_void_p(stream)))
+
+    def scatter_hard(self, d_c_hat_dense, d_iters_dense, d_index, d_count, d_c_hat, d_iters=None, stream=0):
+        """nrldpc_mix_scatter_hard_dev on raw device addresses: row d_index[off[i].cb + j] of d_c_hat (in/out) = dense row j; rows of
+        blocks that are not pending keep what they held, their d_iters entries become 0."""
+        check(self._skip_fn("nrldpc_mix_scatter_hard_dev")(self._h, _ptr(d_c_hat_dense), _ptr(d_iters_dense), _ptr(d_index), _ptr(d_count),
+                                                           _ptr(d_c_hat), _ptr(d_iters), C.c_void_p(stream)))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

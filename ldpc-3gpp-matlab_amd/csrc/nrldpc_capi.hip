@@ -38,6 +38,7 @@
 #include "nrldpc_modem.h"
 #include "nrldpc_ratematch_ex.h"
 #include "nrldpc_mix.h"
+#include "nrldpc_mix_skip.h"
 #include "nrldpc_mix_tx.h"
 #include "nrldpc_rm_core.h"
 
@@ -2160,6 +2161,9 @@ struct nrldpc_mix {
     char* blob = nullptr;                // every device table, one allocation, written once by nrldpc_mix_create
     nrldpc::MixRmLaunch rm{};
     nrldpc::MixCrcLaunch crc{};
+    nrldpc::MixSkipLaunch skip{};        // nrldpc_mix_pending_dev / _gather_cw_dev / _scatter_hard_dev: the records; prefix, n_wg and esize per call
+    const int32_t* skip_prefix[3] = {nullptr, nullptr, nullptr}; // device, [n + 1] each: the grids over f32 rows, f16 rows, hard-bit rows
+    int32_t skip_wg[3] = {0, 0, 0};
 };
 
 namespace {
@@ -2170,6 +2174,8 @@ struct MixHost {
     std::vector<nrldpc::MixRmRec> rm;
     std::vector<nrldpc::MixCrcRec> crc;
     std::vector<int32_t> rm_prefix, tb_prefix, e_tab, off_tab;
+    std::vector<nrldpc::MixSkipRec> skip;
+    std::vector<int32_t> skip_prefix[3]; // f32 rows, f16 rows, hard-bit rows
     int64_t used[nrldpc::MIX_FIELDS] = {0, 0, 0, 0, 0, 0, 0};
     int32_t k_max = 0, c_max = 0;
 };
@@ -2241,6 +2247,25 @@ int mix_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool ta
         make_crc_plan(&c.tb, crc_poly_for(q->tb_crc_len, false), q->tb_crc_len, pay, pay, pay);
         make_crc_plan(&c.cb, crc_poly_for(24, true), 24, q->K_prime, 0, 0);
     }
+    if (tables) {
+        // the pending / gather / scatter stages: a record per configuration and a grid per row type, sized for every row.  No grid exceeds
+        // the rate-recovery grid checked above (8192 bytes of f32 are its 2048 positions; f16 and hard-bit rows are shorter).
+        static_assert(nrldpc::MIX_SKIP_CHUNK == 4 * nrldpc::MIX_RM_WG, "the f32 gather grid is the rate-recovery grid");
+        const int32_t esize[3] = {nrldpc::MIX_SKIP_ROW_F32, nrldpc::MIX_SKIP_ROW_F16, nrldpc::MIX_SKIP_ROW_HARD};
+        m.skip.resize(n);
+        for (int k = 0; k < 3; ++k) m.skip_prefix[k].assign((size_t)n + 1, 0);
+        for (int i = 0; i < n; ++i) {
+            nrldpc::MixSkipRec& s = m.skip[i];
+            memset(&s, 0, sizeof s);
+            s.cw_off = m.off[i].cw; s.c_hat_off = m.off[i].c_hat; s.cb_off = m.off[i].cb; s.tb_off = m.off[i].tb;
+            s.n_cb = n_tb[i] * p[i].C; s.C = p[i].C; s.N_cw = 2 * p[i].Z + p[i].N; s.K = p[i].K;
+            for (int k = 0; k < 3; ++k) {
+                const int64_t wgs = m.skip_prefix[k][i] + (int64_t)s.n_cb * nrldpc::mix_skip_chunks(nrldpc::mix_skip_row_bytes(s, esize[k]));
+                if (wgs > INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
+                m.skip_prefix[k][i + 1] = (int32_t)wgs;
+            }
+        }
+    }
     return NRLDPC_OK;
 }
 
@@ -2292,7 +2317,8 @@ int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb,
     auto pad16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_rm = 0, o_crc = o_rm + pad16(mh.rm.size() * sizeof(nrldpc::MixRmRec)), o_rp = o_crc + pad16(mh.crc.size() * sizeof(nrldpc::MixCrcRec)),
                  o_tp = o_rp + pad16(mh.rm_prefix.size() * 4), o_e = o_tp + pad16(mh.tb_prefix.size() * 4), o_o = o_e + pad16(mh.e_tab.size() * 4),
-                 o_tbo = o_o + pad16(mh.off_tab.size() * 4), total = o_tbo + pad16((size_t)n * 8);
+                 o_tbo = o_o + pad16(mh.off_tab.size() * 4), o_sk = o_tbo + pad16((size_t)n * 8), o_sp = o_sk + pad16(mh.skip.size() * sizeof(nrldpc::MixSkipRec)),
+                 sp_len = pad16(((size_t)n + 1) * 4), total = o_sp + 3 * sp_len;
     std::vector<char> img(total, 0);
     memcpy(img.data() + o_rm, mh.rm.data(), mh.rm.size() * sizeof(nrldpc::MixRmRec));
     memcpy(img.data() + o_crc, mh.crc.data(), mh.crc.size() * sizeof(nrldpc::MixCrcRec));
@@ -2301,6 +2327,8 @@ int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb,
     memcpy(img.data() + o_e, mh.e_tab.data(), mh.e_tab.size() * 4);
     memcpy(img.data() + o_o, mh.off_tab.data(), mh.off_tab.size() * 4);
     for (int i = 0; i < n; ++i) memcpy(img.data() + o_tbo + (size_t)i * 8, &mh.off[i].tb, 8);
+    memcpy(img.data() + o_sk, mh.skip.data(), mh.skip.size() * sizeof(nrldpc::MixSkipRec));
+    for (int k = 0; k < 3; ++k) memcpy(img.data() + o_sp + k * sp_len, mh.skip_prefix[k].data(), mh.skip_prefix[k].size() * 4);
     DeviceScope scope(device_id);
     hipError_t e = scope.err;
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->blob), total);
@@ -2313,6 +2341,12 @@ int nrldpc_mix_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb,
     m->rm.e_tab = reinterpret_cast<const int32_t*>(m->blob + o_e);
     m->rm.off_tab = reinterpret_cast<const int32_t*>(m->blob + o_o);
     m->tb_offs = reinterpret_cast<const int64_t*>(m->blob + o_tbo);
+    m->skip.recs = reinterpret_cast<const nrldpc::MixSkipRec*>(m->blob + o_sk);
+    m->skip.n = n;
+    for (int k = 0; k < 3; ++k) {
+        m->skip_prefix[k] = reinterpret_cast<const int32_t*>(m->blob + o_sp + k * sp_len);
+        m->skip_wg[k] = mh.skip_prefix[k][n];
+    }
     *out = m;
     return NRLDPC_OK;
     NRLDPC_API_END
@@ -2387,6 +2421,54 @@ int nrldpc_mix_crc_check_harq_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat, u
     if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
     hipError_t e = nrldpc::launch_mix_crc_check_harq(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hipfail(e, "mix CRC kernel launch");
+    return NRLDPC_OK;
+}
+
+// ---- HARQ steps that decode only the pending code blocks (kernels: nrldpc_mix_skip.hip; the rule and the mapping: nrldpc_mix_skip.h) ----
+int nrldpc_mix_pending_dev(nrldpc_mix_handle m, int32_t rule, const int32_t* d_cb_pass, const int32_t* d_ok, const uint8_t* d_cbgti,
+                           const uint8_t* d_new, int32_t* d_index, int32_t* d_count, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if (rule != NRLDPC_MIX_SKIP_UNSCHEDULED && rule != NRLDPC_MIX_SKIP_SETTLED)
+        return fail(NRLDPC_ERR_UNSUPPORTED, "rule must be NRLDPC_MIX_SKIP_UNSCHEDULED or NRLDPC_MIX_SKIP_SETTLED");
+    if (m->size_cb == 0) return NRLDPC_OK; // the empty plan: no tables, no launch
+    if (!d_index || !d_count) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (rule == NRLDPC_MIX_SKIP_SETTLED && (!d_cb_pass || !d_ok)) return fail(NRLDPC_ERR_ARG, "the settled rule needs d_cb_pass and d_ok");
+    nrldpc::MixSkipState s;
+    s.cb_pass = d_cb_pass; s.ok = d_ok; s.cbgti = d_cbgti; s.is_new = d_new;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_skip_pending(m->skip, rule, s, d_index, d_count, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix pending kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_gather_cw_dev(nrldpc_mix_handle m, const void* d_cw_llr, int32_t dtype, const int32_t* d_index, const int32_t* d_count,
+                             void* d_cw_dense, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if (dtype != NRLDPC_LLR_F32 && dtype != NRLDPC_LLR_F16) return fail(NRLDPC_ERR_UNSUPPORTED, "dtype must be f32 or f16");
+    if (m->size_cb == 0) return NRLDPC_OK;
+    if (!d_cw_llr || !d_index || !d_count || !d_cw_dense) return fail(NRLDPC_ERR_ARG, "null pointer");
+    const int k = dtype == NRLDPC_LLR_F32 ? 0 : 1;
+    nrldpc::MixSkipLaunch a = m->skip; // (a copy: calls in flight on several streams share the plan, never a launch block)
+    a.prefix = m->skip_prefix[k]; a.n_wg = m->skip_wg[k]; a.esize = k == 0 ? nrldpc::MIX_SKIP_ROW_F32 : nrldpc::MIX_SKIP_ROW_F16;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_skip_gather(a, d_cw_llr, d_index, d_count, d_cw_dense, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix gather kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_scatter_hard_dev(nrldpc_mix_handle m, const uint8_t* d_c_hat_dense, const int32_t* d_iters_dense, const int32_t* d_index,
+                                const int32_t* d_count, uint8_t* d_c_hat, int32_t* d_iters, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if (m->size_cb == 0) return NRLDPC_OK;
+    if (!d_c_hat_dense || !d_index || !d_count || !d_c_hat) return fail(NRLDPC_ERR_ARG, "null pointer");
+    nrldpc::MixSkipLaunch a = m->skip;
+    a.prefix = m->skip_prefix[2]; a.n_wg = m->skip_wg[2]; a.esize = nrldpc::MIX_SKIP_ROW_HARD;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_skip_scatter(a, d_c_hat_dense, d_iters_dense, d_index, d_count, d_c_hat, d_iters, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix scatter kernel launch");
     return NRLDPC_OK;
 }
 

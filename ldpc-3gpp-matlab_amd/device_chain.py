@@ -8,7 +8,7 @@ import copy
 
 import numpy as np
 
-from ._capi import LLR_F16, LLR_F32, MIX_FIELDS, Codec, MixPlan, MixTxPlan, MultiCall, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
+from ._capi import LLR_F16, LLR_F32, MIX_FIELDS, MIX_SKIP_SETTLED, MIX_SKIP_UNSCHEDULED, Codec, MixPlan, MixTxPlan, MultiCall, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
 from .nrldpc import NRLDPC
 
 
@@ -165,13 +165,24 @@ class MixedDecodeChain:
     or f16 by harq_dtype), `cb_pass` (the sticky code_block_CRC_passed), `cbgti` (CBGTI_flags of each parameter object, filled once)
     and `b_hat`, which becomes in/out (b_hat_buffer) -- and step() takes the redundancy version(s) and a per-transport-block "starts
     a new HARQ process" flag array; reset() clears the state of every block (:343-356), a flag that of one block.  A plan is immutable
-    and rv_id only moves k_0, so the chain holds one MixPlan per distinct tuple of redundancy versions over the same arrays."""
+    and rv_id only moves k_0, so the chain holds one MixPlan per distinct tuple of redundancy versions over the same arrays.
 
+    skip (only with I_HARQ != 0; None, the default, is the chain described so far, on the same code path): a step decodes only the code
+    blocks still PENDING -- MixPlan.pending turns the state into an index list and a count per configuration, the counts come to the
+    host (the one synchronisation the mode adds), and unless every block is pending MixPlan.gather_cw packs the pending LLR rows, the
+    decoder runs on counts[i] rows and MixPlan.scatter_hard puts the hard decisions back.  "unscheduled": pending = the block's CBGTI
+    flag; b_hat, ok and cb_pass are bit for bit those of skip=None.  "settled": also leaves out blocks whose CRC held in an earlier
+    step and transport blocks already acknowledged (the rule: include/nrldpc.h); a settled block keeps the hard decisions of the step
+    in which it settled instead of being decoded again -- a deviation from the reference -- and `ok` and `c_hat` become state, which
+    reset() clears.  After a step last_decoded lists the code blocks decoded per configuration, `index` and `count` are the device
+    arrays of MixPlan.pending, iters is 0 for a block that was not decoded."""
+
+    _SKIP_RULES = {"unscheduled": MIX_SKIP_UNSCHEDULED, "settled": MIX_SKIP_SETTLED}
     _SHAPES = {"g": lambda t, n: (n, t.G), "harq": lambda t, n: (n, t.C, t.N_cb), "cw": lambda t, n: (n * t.C, 2 * t.Z + t.N),
                "c_hat": lambda t, n: (n * t.C, t.K), "cb": lambda t, n: (n, t.C), "b_hat": lambda t, n: (n, t.B), "tb": lambda t, n: (n,)}
 
     def __init__(self, params, n_tb, iterations=50, alpha=None, beta=0.0, llr_scale=0, prune_layers=True, llr_dtype=None,
-                 algorithm="min-sum", device_id=0, I_HARQ=0, harq_dtype=None):
+                 algorithm="min-sum", device_id=0, I_HARQ=0, harq_dtype=None, skip=None):
         algorithm_code(algorithm)  # UnsupportedParameters for an unknown name, before any device work
         try:
             self.harq_dtype = np.dtype(np.float32 if harq_dtype is None else harq_dtype)
@@ -180,6 +191,13 @@ class MixedDecodeChain:
         if self.harq_dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
             raise UnsupportedParameters("harq_dtype should be numpy float32 or float16, not %r." % (harq_dtype,))
         self.I_HARQ = int(I_HARQ)
+        if skip is not None and (not isinstance(skip, str) or skip not in self._SKIP_RULES):
+            raise UnsupportedParameters("skip should be None, \"unscheduled\" or \"settled\", not %r." % (skip,))
+        if skip is not None and not self.I_HARQ:
+            raise UnsupportedParameters("skip=%r reads HARQ state: it needs I_HARQ ~= 0." % (skip,))
+        self.skip = skip
+        self.last_decoded = None
+        self.index = self.count = self._count_host = self._dense = None
         import torch
         self.torch = torch
         params = list(params)
@@ -227,6 +245,10 @@ class MixedDecodeChain:
             self._multi = MultiCall(self.codecs, [self.cw_llr.data_ptr() + off[i].cw * self.llr_dtype.itemsize for i in range(n)],
                                     [self.n_tb[i] * params[i].C for i in range(n)], [self.c_hat.data_ptr() + off[i].c_hat for i in range(n)],
                                     [self.iters.data_ptr() + 4 * off[i].cb for i in range(n)]) if n else None
+            if self.skip is not None and self._multi is not None:
+                self.index = torch.zeros(tot.cb, dtype=torch.int32, device=self.dev)
+                self.count = torch.zeros(n, dtype=torch.int32, device=self.dev)
+                self._count_host = torch.zeros(n, dtype=torch.int32).pin_memory()
         except Exception:
             self.close()
             raise
@@ -235,7 +257,7 @@ class MixedDecodeChain:
         for c in getattr(self, "codecs", []):
             c.close()
         self.codecs = []
-        self._multi = None
+        self._multi = self._dense = None
         for plan in getattr(self, "_plans", {}).values():
             plan.close()
         self._plans = {}
@@ -248,6 +270,9 @@ class MixedDecodeChain:
         for t in (self.harq, self.b_hat, self.cb_pass):
             if t is not None:
                 t.zero_()
+        if self.skip is not None:  # ok is the settled rule's state, c_hat holds the decisions settled blocks keep
+            self.ok.zero_()
+            self.c_hat.zero_()
         self._layers_seen = [4] * len(self.params)
 
     def _plan_for(self, rv_id):
@@ -357,11 +382,46 @@ class MixedDecodeChain:
                                    self.cw_llr.data_ptr(), d_new, in_dtype=LLR_F16 if g.dtype == f16 else LLR_F32,
                                    harq_dtype=LLR_F16 if self.harq_dtype == np.float16 else LLR_F32,
                                    out_dtype=LLR_F16 if self.llr_dtype == np.float16 else LLR_F32, stream=stream)
-            if self._multi is not None:
+            if self.skip is not None:
+                self._decode_pending(plan, d_new, stream)
+            elif self._multi is not None:
                 self._multi(stream)
             plan.crc_check_harq(self.c_hat.data_ptr(), self.b_hat.data_ptr(), self.ok.data_ptr(), self.cb_pass.data_ptr(),
                                 self.cbgti.data_ptr(), d_new, stream=stream)
         return self.b_hat, self.ok, self.iters
+
+    def _decode_pending(self, plan, d_new, stream):
+        """The decoder stage of a step with skip set: the pending code blocks only (self.ok still holds the previous step's flags)."""
+        torch, n = self.torch, len(self.params)
+        totals = [k * p.C for k, p in zip(self.n_tb, self.params)]
+        if self._multi is None or not any(totals):  # the empty mix
+            self.last_decoded = [0] * n
+            return
+        plan.pending(self._SKIP_RULES[self.skip], self.cb_pass.data_ptr(), self.ok.data_ptr(), self.cbgti.data_ptr(), d_new,
+                     self.index.data_ptr(), self.count.data_ptr(), stream=stream)
+        self._count_host.copy_(self.count, non_blocking=True)
+        torch.cuda.current_stream(self.dev).synchronize()  # the one synchronisation of the mode: the decoder's batch sizes are host arguments
+        counts = self.last_decoded = [int(x) for x in self._count_host.tolist()]
+        if counts == totals:  # everything is pending: the step of skip=None
+            self._multi(stream)
+            return
+        if self._dense is None:  # the dense arrays (the layout and totals of the full ones) and their decoder call, on first need
+            tot, off = self.plan.totals, self.plan.offsets
+            cw = torch.zeros(tot.cw, dtype=self.cw_llr.dtype, device=self.dev)
+            c_hat = torch.zeros(tot.c_hat, dtype=torch.uint8, device=self.dev)
+            iters = torch.zeros(tot.cb, dtype=torch.int32, device=self.dev)
+            multi = MultiCall(self.codecs, [cw.data_ptr() + off[i].cw * self.llr_dtype.itemsize for i in range(n)], [0] * n,
+                              [c_hat.data_ptr() + off[i].c_hat for i in range(n)], [iters.data_ptr() + 4 * off[i].cb for i in range(n)])
+            self._dense = (cw, c_hat, iters, multi)
+        cw, c_hat, iters, multi = self._dense
+        if any(counts):
+            plan.gather_cw(self.cw_llr.data_ptr(), self.index.data_ptr(), self.count.data_ptr(), cw.data_ptr(),
+                           dtype=LLR_F16 if self.llr_dtype == np.float16 else LLR_F32, stream=stream)
+            for i, k in enumerate(counts):
+                multi.bt[i] = k
+            multi(stream)
+        plan.scatter_hard(c_hat.data_ptr(), iters.data_ptr(), self.index.data_ptr(), self.count.data_ptr(), self.c_hat.data_ptr(),
+                          self.iters.data_ptr(), stream=stream)
 
 
 class DeviceEncodeChain:
