@@ -671,6 +671,84 @@ int nrldpc_awgn_dev(const float* d_tx /* [n_sym][2] */, int64_t n_sym,
                     uint64_t seed, uint64_t first_symbol,
                     float* d_rx /* [n_sym][2]; may equal d_tx */, void* stream);
 
+/* ---- mixed transport-block batches, the channel leg: one launch per stage ------------------------------------------------------------
+ * The leg between the transmit plan (nrldpc_mix_tx_*) and the receive plan (nrldpc_mix_*) for a batch whose transport blocks differ
+ * in modulation order and operating point: the four calls above -- nrldpc_awgn_llr_dev, nrldpc_modulate_dev, nrldpc_awgn_dev,
+ * nrldpc_demodulate_dev -- over every configuration of a mix in ONE launch each.  (The transmit-plan block above lists "a mixed-batch
+ * channel stage" as out of scope; this block, added after it, is that stage.)  A CHANNEL PLAN is built from the same (n, p[], n_tb[])
+ * as the other two plans, is immutable and owns one device allocation of tables, uploaded synchronously by nrldpc_mix_chan_create and
+ * never written again: calls in flight on several streams may share one plan.  nrldpc_mix_chan_handle is a type of its own; the
+ * receive and transmit plans are unchanged.  Added without a revision bump (NRLDPC_ABI_VERSION stays 6): a binding finds the
+ * functions by symbol.
+ *
+ * Layout.  Bits and LLRs use field g of nrldpc_mix_layout element for element: the transmit plan's packed g goes in, the receive
+ *   plan's packed g_tilde comes out.  Only the symbol array is new: configuration i holds n_sym_i = n_tb[i]*G_i/Q_m_i symbols (a
+ *   symbol never straddles transport blocks: E_r is a multiple of Q_m); sym_off[0] = 0, sym_off[i+1] = round_up(sym_off[i] + n_sym_i,
+ *   16) in SYMBOLS, entry [n] = the total (nrldpc_mix_chan_layout; host only).  Symbol s of configuration i is the float pair at
+ *   2*(sym_off[i] + s), its entry in a per-symbol variance array the float at sym_off[i] + s.  Gap elements are never read or
+ *   written.  nrldpc_mix_offsets keeps its 56 bytes.
+ *
+ * Operating points vary per call and are not part of the plan: one 32-byte nrldpc_mix_chan_point per configuration in a caller-owned
+ *   DEVICE array of n records (host arrays do not fit a kernel argument block at n ~ 100).  nrldpc_mix_chan_point_set (host only) does
+ *   the host arithmetic of nrldpc_awgn_llr_dev: n0 = pow(10, -EsN0_dB/10) in double, then variance = (float)n0, sigma =
+ *   (float)sqrt(n0/2), inv_n0 = (float)(1/n0), each narrowed once; "EsN0_dB out of range" outside (-60, 80) dB.  A caller with its own
+ *   noise figure writes variance, seed and first_symbol directly (the stand-alone stages read no other field).  Records are read on
+ *   the device and not validated there: non-positive or non-finite values, and first_symbol + n_sym_i past 2^64, are unspecified, as
+ *   for the per-symbol arrays of the single calls.
+ *
+ * Semantics, by equality.  In every segment
+ *   nrldpc_mix_chan_awgn_llr_dev   leaves what nrldpc_awgn_llr_dev(g + off[i].g, n_tb[i]*G_i, Q_m_i, EsN0_i, seed_i, first_symbol_i,
+ *                                  g_tilde + off[i].g, stream) leaves, for the EsN0_i the record was set from,
+ *   nrldpc_mix_chan_modulate_dev   leaves what nrldpc_modulate_dev(g + off[i].g, n_tb[i]*G_i, Q_m_i, tx + 2*sym_off[i], stream) leaves,
+ *   nrldpc_mix_chan_awgn_dev       leaves what nrldpc_awgn_dev(tx + 2*sym_off[i], n_sym_i, pt[i].variance, d_variance ? d_variance +
+ *                                  sym_off[i] : NULL, seed_i, first_symbol_i, rx + 2*sym_off[i], stream) leaves; d_rx == d_tx is allowed,
+ *   nrldpc_mix_chan_demodulate_dev leaves what nrldpc_demodulate_dev(rx + 2*sym_off[i], n_sym_i, Q_m_i, method, pt[i].variance,
+ *                                  d_variance ? d_variance + sym_off[i] : NULL, out + off[i].g (in elements of the output type),
+ *                                  out_dtype, stream) leaves: all three methods, f32 or clamped f16 LLRs, hard-bit bytes; d_pt is not
+ *                                  read for NRLDPC_DEMOD_HARD, nor when d_variance is given,
+ *   bit for bit.  The mapper, the noise stage and the demapper are compiled without floating-point contraction, as their single forms
+ *   are: every operation is one IEEE operation or one deterministic hardware instruction.  The fused stage is compiled with
+ *   contraction allowed, as nrldpc_awgn_llr_dev's kernel is; its equality with that kernel rests on the compiler fusing the same
+ *   multiply-adds in the shared per-symbol code, which it does (the floating-point instruction sequences of the two code objects are
+ *   equal, profiles/r10_mix_chan_isa.txt, and tests/test_mix_chan_gpu.py holds the two to bit equality on the device): the contract
+ *   of the fused stage is BIT EQUALITY as well, not the fall-back tolerance.
+ *   Each call is one launch whatever n and only enqueues (no allocation, copy or synchronisation); one writer per element, no atomics;
+ *   results do not depend on which configurations share a plan or on how a mix is split into plans.  Any address the element types
+ *   allow is served: any byte address for bit and hard-bit arrays, 2-byte for f16, 4-byte for floats.
+ *
+ * Refusals, all before any device call.  nrldpc_mix_chan_layout and nrldpc_mix_chan_create refuse what nrldpc_mix_layout /
+ *   nrldpc_mix_create refuse, with the same codes and texts and " (configuration i)" appended, and a Q_m outside {1, 2, 4, 6, 8} with
+ *   "Unsupported modulation (configuration i)", NRLDPC_ERR_UNSUPPORTED; a mix too large for one launch gets the existing text.  n == 0
+ *   or all counts zero is a valid empty plan that needs no device: every stage call on it returns NRLDPC_OK without a launch.  Stage
+ *   calls refuse a null plan, a null base pointer of a non-empty array and a null d_pt where it is read with NRLDPC_ERR_ARG, an unknown
+ *   method or a dtype other than F32 / F16 with NRLDPC_ERR_UNSUPPORTED and the single calls' texts.
+ *
+ * Out of scope: pool variants, the MEX gateway, a mixed payload draw, f16 output of the fused stage, a fused form with per-symbol
+ *   variance.  Measurements against the loop of single calls: DESIGN.md section 4.20. */
+typedef struct nrldpc_mix_chan* nrldpc_mix_chan_handle;
+
+typedef struct nrldpc_mix_chan_point {
+    float variance;               /* N0: read by the stand-alone noise and demapper stages */
+    float sigma, inv_n0;          /* sqrt(N0/2), 1/N0 as nrldpc_awgn_llr_dev forms them: read by the fused stage */
+    uint32_t reserved;            /* 0 */
+    uint64_t seed, first_symbol;  /* Philox key; global index of the configuration's local symbol 0 */
+} nrldpc_mix_chan_point;          /* sizeof == 32 (the library static_asserts it) */
+
+/* host functions, no device: sym_off has n + 1 entries (in symbols) */
+int nrldpc_mix_chan_layout(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int64_t* sym_off);
+int nrldpc_mix_chan_point_set(float EsN0_dB, uint64_t seed, uint64_t first_symbol, nrldpc_mix_chan_point* out);
+
+int nrldpc_mix_chan_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int32_t device_id, nrldpc_mix_chan_handle* out);
+void nrldpc_mix_chan_destroy(nrldpc_mix_chan_handle m);
+
+int nrldpc_mix_chan_awgn_llr_dev(nrldpc_mix_chan_handle m, const uint8_t* d_g, const nrldpc_mix_chan_point* d_pt,
+                                 float* d_g_tilde, void* stream);
+int nrldpc_mix_chan_modulate_dev(nrldpc_mix_chan_handle m, const uint8_t* d_g, float* d_tx, void* stream);
+int nrldpc_mix_chan_awgn_dev(nrldpc_mix_chan_handle m, const float* d_tx, const nrldpc_mix_chan_point* d_pt,
+                             const float* d_variance /* nullable, packed symbol layout */, float* d_rx /* may equal d_tx */, void* stream);
+int nrldpc_mix_chan_demodulate_dev(nrldpc_mix_chan_handle m, const float* d_rx, int32_t method, const nrldpc_mix_chan_point* d_pt,
+                                   const float* d_variance /* nullable */, void* d_out /* field g */, int32_t out_dtype, void* stream);
+
 /* Kernel timing: when enabled, every *_dev / host call records HIP events around its kernel on the
  * launch stream; nrldpc_last_kernel_ms synchronises on the stop event and returns the duration. */
 int nrldpc_set_timing(nrldpc_handle h, int32_t enabled);

@@ -106,6 +106,14 @@ class MixOffsets(C.Structure):
 
 MIX_FIELDS = tuple(k for k, _ in MixOffsets._fields_)
 
+
+class MixChanPoint(C.Structure):
+    """nrldpc_mix_chan_point: the operating point of one configuration of a channel plan (32 bytes; a device array of n of them goes
+    to every stage call).  variance = N0 is what the stand-alone noise and demapper stages read; sigma = sqrt(N0/2) and inv_n0 = 1/N0
+    what the fused stage reads; seed is the Philox key, first_symbol the global index of the configuration's local symbol 0."""
+    _fields_ = [("variance", C.c_float), ("sigma", C.c_float), ("inv_n0", C.c_float), ("reserved", C.c_uint32),
+                ("seed", C.c_uint64), ("first_symbol", C.c_uint64)]
+
 EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_dev", "nrldpc_crc_check_harq_dev", "nrldpc_crc_attach_dev", "nrldpc_rate_match_dev", "nrldpc_create", "nrldpc_destroy", "nrldpc_get_dims", "nrldpc_decode", "nrldpc_decode_dev",
            "nrldpc_decode_multi_dev", "nrldpc_quantise_llr", "nrldpc_encode", "nrldpc_encode_dev", "nrldpc_set_timing", "nrldpc_last_kernel_ms",
            "nrldpc_set_index", "nrldpc_lifting_size", "nrldpc_default_rule", "nrldpc_strerror", "nrldpc_last_error",
@@ -119,7 +127,9 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_mix_rate_recover_harq_dev", "nrldpc_mix_crc_check_harq_dev",
            "nrldpc_mix_pending_dev", "nrldpc_mix_gather_cw_dev", "nrldpc_mix_scatter_hard_dev",
            "nrldpc_mix_tx_layout", "nrldpc_mix_tx_create", "nrldpc_mix_tx_destroy", "nrldpc_mix_tx_crc_attach_dev", "nrldpc_mix_tx_encode_dev",
-           "nrldpc_mix_tx_rate_match_dev", "nrldpc_mix_tx_encode_all_dev"]
+           "nrldpc_mix_tx_rate_match_dev", "nrldpc_mix_tx_encode_all_dev",
+           "nrldpc_mix_chan_layout", "nrldpc_mix_chan_point_set", "nrldpc_mix_chan_create", "nrldpc_mix_chan_destroy",
+           "nrldpc_mix_chan_awgn_llr_dev", "nrldpc_mix_chan_modulate_dev", "nrldpc_mix_chan_awgn_dev", "nrldpc_mix_chan_demodulate_dev"]
 
 _lib = None
 
@@ -219,6 +229,16 @@ def load():
         L.nrldpc_mix_tx_rate_match_dev.argtypes = [vp, vp, vp, vp]
     if hasattr(L, "nrldpc_mix_tx_encode_all_dev"):  # the encode stage in one launch, found by symbol like the rest
         L.nrldpc_mix_tx_encode_all_dev.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "nrldpc_mix_chan_create"):  # the channel leg of the mixed batches, found by symbol like the rest
+        L.nrldpc_mix_chan_layout.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), C.POINTER(C.c_int64)]
+        L.nrldpc_mix_chan_point_set.argtypes = [C.c_float, C.c_uint64, C.c_uint64, C.POINTER(MixChanPoint)]
+        L.nrldpc_mix_chan_create.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), i32, C.POINTER(vp)]
+        L.nrldpc_mix_chan_destroy.argtypes = [vp]
+        L.nrldpc_mix_chan_destroy.restype = None
+        L.nrldpc_mix_chan_awgn_llr_dev.argtypes = [vp, vp, vp, vp, vp]
+        L.nrldpc_mix_chan_modulate_dev.argtypes = [vp, vp, vp, vp]
+        L.nrldpc_mix_chan_awgn_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.nrldpc_mix_chan_demodulate_dev.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp]
     L.nrldpc_crc_attach_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_rate_match_dev.argtypes = [C.POINTER(TbParams), vp, i32, vp, vp]
     L.nrldpc_pool_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), i32, i32, C.POINTER(vp)]
@@ -857,6 +877,99 @@ def awgn_dev(d_tx, n_sym, d_rx, variance=1.0, d_variance=None, seed=0, first_sym
         raise NRLDPCError("first_symbol should lie in [0, 2^64)")
     check(L.nrldpc_awgn_dev(_ptr(d_tx), int(n_sym), float(variance), _ptr(d_variance), int(seed) % (1 << 64), int(first_symbol),
                             _ptr(d_rx), C.c_void_p(stream or 0)))
+
+
+def _mix_chan_lib():
+    L = _mix_lib()
+    if not hasattr(L, "nrldpc_mix_chan_create"):
+        raise NRLDPCError("%s has no nrldpc_mix_chan_create: the channel leg of mixed transport-block batches needs a library built "
+                          "from this tree (NRLDPC_LIB selects an older one?)" % lib_path())
+    return L
+
+
+def mix_chan_layout(params, n_tb):
+    """nrldpc_mix_chan_layout: the n + 1 offsets, in SYMBOLS, of the packed symbol array of a mix ([n]: the total).  Symbol s of
+    configuration i is the float pair at 2 * (sym_off[i] + s), its per-symbol variance the float at sym_off[i] + s.  Bits and LLRs use
+    mix_layout's field g.  Host function, no device needed."""
+    n, ts, nt = _mix_args(params, n_tb)
+    sym_off = (C.c_int64 * (n + 1))()
+    check(_mix_chan_lib().nrldpc_mix_chan_layout(n, ts, nt, sym_off))
+    return [int(x) for x in sym_off]
+
+
+class MixChanPlan:
+    """nrldpc_mix_chan_*: the channel leg between MixTxPlan and MixPlan -- an immutable plan for a batch whose transport blocks differ
+    in modulation order.  .sym_off: the n + 1 offsets of the packed symbol array, in symbols; .off: the receive layout's n + 1
+    MixOffsets records, of which the bits and the LLRs use g; totals(): {"g", "sym"} -> elements to allocate (2 floats per symbol).
+    points() makes the n operating-point records a stage call reads from DEVICE memory.  awgn_llr() (fused), modulate(), awgn() and
+    demodulate() are one launch each, whatever n.  Streams may share a plan."""
+
+    def __init__(self, params, n_tb, device_id=0):
+        self._h = C.c_void_p()
+        self._lib = L = _mix_chan_lib()
+        self.n, ts, nt = _mix_args(params, n_tb)
+        self.n_tb = [int(x) for x in n_tb]
+        self.device_id = int(device_id)
+        sym_off = (C.c_int64 * (self.n + 1))()
+        check(L.nrldpc_mix_chan_layout(self.n, ts, nt, sym_off))
+        self.sym_off = [int(x) for x in sym_off]
+        off = (MixOffsets * (self.n + 1))()
+        check(L.nrldpc_mix_layout(self.n, ts, nt, off))
+        self.off = list(off)
+        self.params = [ts[i] for i in range(self.n)]
+        self._ts = ts  # (the records above are views of this array)
+        check(L.nrldpc_mix_chan_create(self.n, ts, nt, self.device_id, C.byref(self._h)))
+
+    def totals(self):
+        """Elements to allocate: "g" bits / LLRs / hard bits, "sym" symbols (two floats each; one float each in a variance array)."""
+        return {"g": self.off[self.n].g, "sym": self.sym_off[self.n]}
+
+    def points(self, EsN0_dB, seed, first_symbol=0):
+        """The n nrldpc_mix_chan_point records of one call as a ctypes array (nrldpc_mix_chan_point_set per configuration; host only):
+        EsN0_dB, seed and first_symbol are sequences of n values or scalars, which broadcast.  Copy the array to the device (it is
+        32 * n bytes; np.frombuffer(pts, np.uint8) views it) and hand its address to the stage calls."""
+        def spread(x, what):
+            xs = list(x) if hasattr(x, "__len__") else [x] * self.n
+            if len(xs) != self.n:
+                raise NRLDPCError("one %s per configuration expected (%d), got %d." % (what, self.n, len(xs)))
+            return xs
+        es, sd, fs = spread(EsN0_dB, "EsN0_dB"), spread(seed, "seed"), spread(first_symbol, "first_symbol")
+        pts = (MixChanPoint * max(self.n, 1))()
+        for i in range(self.n):
+            if not 0 <= int(fs[i]) < 1 << 64:
+                raise NRLDPCError("first_symbol should lie in [0, 2^64)")
+            check(self._lib.nrldpc_mix_chan_point_set(float(es[i]), int(sd[i]) % (1 << 64), int(fs[i]), C.byref(pts[i])))
+        return pts
+
+    def awgn_llr(self, d_g, d_pt, d_g_tilde, stream=0):
+        """nrldpc_mix_chan_awgn_llr_dev on raw device addresses: packed bits -> packed f32 LLRs, mapper + noise + exact demapper fused."""
+        check(self._lib.nrldpc_mix_chan_awgn_llr_dev(self._h, _ptr(d_g), _ptr(d_pt), _ptr(d_g_tilde), C.c_void_p(stream)))
+
+    def modulate(self, d_g, d_tx, stream=0):
+        """nrldpc_mix_chan_modulate_dev on raw device addresses: packed bits -> packed symbols."""
+        check(self._lib.nrldpc_mix_chan_modulate_dev(self._h, _ptr(d_g), _ptr(d_tx), C.c_void_p(stream)))
+
+    def awgn(self, d_tx, d_pt, d_rx, d_variance=None, stream=0):
+        """nrldpc_mix_chan_awgn_dev on raw device addresses: d_rx may be d_tx; d_variance (packed symbol layout, one float per symbol)
+        replaces the records' variance."""
+        check(self._lib.nrldpc_mix_chan_awgn_dev(self._h, _ptr(d_tx), _ptr(d_pt), _ptr(d_variance), _ptr(d_rx), C.c_void_p(stream)))
+
+    def demodulate(self, d_rx, d_pt, d_out, method="llr", d_variance=None, out_dtype=LLR_F32, stream=0):
+        """nrldpc_mix_chan_demodulate_dev on raw device addresses: packed symbols -> packed LLRs of out_dtype (LLR_F32 / LLR_F16), or
+        hard-bit bytes for method "hard" (method names as in demod_method_code).  d_pt is not read for "hard" or with d_variance."""
+        check(self._lib.nrldpc_mix_chan_demodulate_dev(self._h, _ptr(d_rx), demod_method_code(method), _ptr(d_pt), _ptr(d_variance),
+                                                       _ptr(d_out), int(out_dtype), C.c_void_p(stream)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.nrldpc_mix_chan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def payload_bits_dev(seed, first_block, n_tb, A, d_a, stream=0):

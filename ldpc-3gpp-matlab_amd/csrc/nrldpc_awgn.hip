@@ -21,20 +21,13 @@
 
 #include "nrldpc_modem.h"
 #include "nrldpc_noise.h"
+#include "nrldpc_awgn_sym.h"
 
 namespace nrldpc {
 
 constexpr int AWGN_BLOCK = 256, AWGN_MAX_GRID = 1 << 20;
 
-// (re, im) + the noise of one symbol.  sigma = sqrt(N0 / 2) per rail is formed here from the f32 N0, for the scalar and for the array
-// alike: the two give the same bits.  N0 == 0 gives sigma == 0 and noise +-0: the symbol comes back as the number it was.
-__device__ __forceinline__ void add_noise(uint32_t w1, uint32_t w2, float n0, float& re, float& im) {
-    float rad, cs, sn;
-    box_muller(w1, w2, sqrtf(0.5f * n0), rad, cs, sn);
-    const float ni = rad * cs, nq = rad * sn;
-    re += ni;
-    im += nq;
-}
+// add_noise, (re, im) + the noise of one symbol: nrldpc_awgn_sym.h (shared with nrldpc_mix_modem.hip)
 
 template <bool VAR> __global__ __launch_bounds__(AWGN_BLOCK) void nrldpc_awgn_kernel(const AwgnArgs a, const uint64_t npairs) {
     for (uint64_t p = (uint64_t)blockIdx.x * AWGN_BLOCK + threadIdx.x; p < npairs; p += (uint64_t)gridDim.x * AWGN_BLOCK) {

@@ -40,6 +40,7 @@
 #include "nrldpc_mix.h"
 #include "nrldpc_mix_skip.h"
 #include "nrldpc_mix_tx.h"
+#include "nrldpc_mix_chan.h"
 #include "nrldpc_rm_core.h"
 
 static_assert(sizeof(nrldpc_cw_out) == 32, "nrldpc_cw_out: the size include/nrldpc.h states");
@@ -2747,6 +2748,200 @@ int nrldpc_mix_tx_rate_match_dev(nrldpc_mix_tx_handle m, const uint8_t* d_cw, ui
     if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
     hipError_t e = nrldpc::launch_mix_tx_rate_match(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hipfail(e, "mix rate-matching kernel launch");
+    return NRLDPC_OK;
+}
+
+} // extern "C"
+
+// ---- mixed transport-block batches, the channel leg (nrldpc_mix_chan_*; kernels: nrldpc_mix_chan.hip and nrldpc_mix_modem.hip, tables and
+// mapping: nrldpc_mix_chan.h) ----
+// A third plan type: the receive plan nrldpc_mix and the transmit plan nrldpc_mix_tx, their blobs and their records are untouched.
+static_assert(sizeof(nrldpc_mix_chan_point) == 32, "nrldpc_mix_chan_point: the size include/nrldpc.h states");
+
+struct nrldpc_mix_chan {
+    int32_t n = 0, device_id = 0;
+    int64_t size_g = 0, size_sym = 0;    // elements in use (sum over configurations): bits / LLRs, symbols
+    char* blob = nullptr;                // every device table, one allocation, written once by nrldpc_mix_chan_create
+    nrldpc::MixChanTables modem{};       // mapper and demapper: a thread per S symbols
+    nrldpc::MixChanTables pair{};        // fused stage and stand-alone noise: a thread per aligned pair of the global symbol count
+};
+
+namespace {
+
+struct MixChanHost {
+    std::vector<int64_t> sym_off;
+    std::vector<nrldpc::MixChanRec> recs;
+    std::vector<int32_t> modem_prefix, pair_prefix;
+    int64_t used_g = 0, used_sym = 0;
+};
+
+// everything the channel plan needs, on the host.  No device call.  The refusals of mix_build, then the modulation order.
+int mix_chan_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, MixChanHost& m) {
+    if (n < 0) return fail(NRLDPC_ERR_ARG, "negative configuration count");
+    if (n > 0 && (!p || !n_tb)) return fail(NRLDPC_ERR_ARG, "null array");
+    m.sym_off.assign((size_t)n + 1, 0);
+    m.modem_prefix.assign((size_t)n + 1, 0);
+    m.pair_prefix.assign((size_t)n + 1, 0);
+    m.recs.resize(n);
+    int64_t g_off = 0, wg_rx = 0, tbs = 0, wg_modem = 0, wg_pair = 0;
+    for (int i = 0; i < n; ++i) {
+        const nrldpc_tb_params* q = p + i;
+        nrldpc::RmExArgs blocks;
+        const int rc = mix_check_cfg(q, n_tb[i], i, blocks);
+        if (rc) return rc;
+        if (q->Q_m != 1 && q->Q_m != 2 && q->Q_m != 4 && q->Q_m != 6 && q->Q_m != 8) return mix_fail_at(fail(NRLDPC_ERR_UNSUPPORTED, "Unsupported modulation"), i);
+        const int64_t bits = (int64_t)n_tb[i] * q->G, n_sym = bits / q->Q_m; // (G is a multiple of Q_m: every E_r is)
+        nrldpc::MixChanRec& r = m.recs[i];
+        memset(&r, 0, sizeof r);
+        r.g_off = g_off; r.sym_off = m.sym_off[i]; r.n_sym = n_sym; r.Qm = q->Q_m;
+        r.inv_norm = (float)(1.0 / std::sqrt(2.0 * kRailMeanSq[q->Q_m / 2]));
+        g_off = nrldpc::mix_round_up(g_off + bits); // field g of nrldpc_mix_layout
+        m.sym_off[i + 1] = nrldpc::mix_chan_sym_next(m.sym_off[i], n_sym);
+        m.used_g += bits; m.used_sym += n_sym;
+        wg_rx += (int64_t)n_tb[i] * q->C * nrldpc::mix_rm_wg_per_cb(2 * q->Z + q->N); // (a plan nrldpc_mix_create refuses is refused here too)
+        tbs += n_tb[i];
+        wg_modem += nrldpc::mix_chan_modem_wgs(n_sym, q->Q_m);
+        wg_pair += nrldpc::mix_chan_pair_wgs(n_sym);
+        if (wg_rx > INT32_MAX || tbs > INT32_MAX || wg_modem > INT32_MAX || wg_pair > INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
+        m.modem_prefix[i + 1] = (int32_t)wg_modem;
+        m.pair_prefix[i + 1] = (int32_t)wg_pair;
+    }
+    return NRLDPC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nrldpc_mix_chan_layout(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int64_t* sym_off) {
+    NRLDPC_API_BEGIN
+    if (n >= 0 && !sym_off) return fail(NRLDPC_ERR_ARG, "null array");
+    MixChanHost m;
+    int rc = mix_chan_build(n, p, n_tb, m);
+    if (rc) return rc;
+    memcpy(sym_off, m.sym_off.data(), m.sym_off.size() * sizeof(int64_t));
+    return NRLDPC_OK;
+    NRLDPC_API_END
+}
+
+int nrldpc_mix_chan_point_set(float EsN0_dB, uint64_t seed, uint64_t first_symbol, nrldpc_mix_chan_point* out) {
+    if (!out) return fail(NRLDPC_ERR_ARG, "null out");
+    if (!(EsN0_dB > -60.0f && EsN0_dB < 80.0f)) return fail(NRLDPC_ERR_ARG, "EsN0_dB out of range");
+    const double n0 = std::pow(10.0, -(double)EsN0_dB / 10.0); // the arithmetic of nrldpc_awgn_llr_dev, each field narrowed once
+    out->variance = (float)n0;
+    out->sigma = (float)std::sqrt(n0 / 2.0); out->inv_n0 = (float)(1.0 / n0);
+    out->reserved = 0;
+    out->seed = seed; out->first_symbol = first_symbol;
+    return NRLDPC_OK;
+}
+
+void nrldpc_mix_chan_destroy(nrldpc_mix_chan_handle m) {
+    if (!m) return;
+    if (m->blob) { DeviceScope scope(m->device_id); (void)hipFree(m->blob); }
+    delete m;
+}
+
+int nrldpc_mix_chan_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, int32_t device_id, nrldpc_mix_chan_handle* out) {
+    NRLDPC_API_BEGIN
+    if (!out) return fail(NRLDPC_ERR_ARG, "null out");
+    *out = nullptr;
+    MixChanHost mh;
+    int rc = mix_chan_build(n, p, n_tb, mh);
+    if (rc) return rc;
+    bool empty = true; // an empty plan: no tables, no launches, no device call at all
+    for (int i = 0; i < n; ++i) empty = empty && n_tb[i] == 0;
+    if (!empty) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+            return fail(NRLDPC_ERR_HIP, "no HIP device available (this library has no CPU path)");
+        if (device_id < 0 || device_id >= ndev) return fail(NRLDPC_ERR_ARG, "device_id out of range");
+    }
+    nrldpc_mix_chan* m = new (std::nothrow) nrldpc_mix_chan();
+    if (!m) return fail(NRLDPC_ERR_NOMEM, "host allocation failed");
+    m->n = n; m->device_id = device_id;
+    m->size_g = mh.used_g; m->size_sym = mh.used_sym;
+    m->modem.n = m->pair.n = n;
+    m->modem.n_wg = mh.modem_prefix[n]; m->pair.n_wg = mh.pair_prefix[n];
+    if (empty) { *out = m; return NRLDPC_OK; }
+    // one allocation, every table at a multiple of 16 bytes, uploaded synchronously and never written again
+    auto pad16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_rec = 0, o_mp = o_rec + pad16(mh.recs.size() * sizeof(nrldpc::MixChanRec)), o_pp = o_mp + pad16(mh.modem_prefix.size() * 4),
+                 total = o_pp + pad16(mh.pair_prefix.size() * 4);
+    std::vector<char> img(total, 0);
+    memcpy(img.data() + o_rec, mh.recs.data(), mh.recs.size() * sizeof(nrldpc::MixChanRec));
+    memcpy(img.data() + o_mp, mh.modem_prefix.data(), mh.modem_prefix.size() * 4);
+    memcpy(img.data() + o_pp, mh.pair_prefix.data(), mh.pair_prefix.size() * 4);
+    DeviceScope scope(device_id);
+    hipError_t e = scope.err;
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->blob), total);
+    if (e == hipSuccess) e = hipMemcpy(m->blob, img.data(), total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { nrldpc_mix_chan_destroy(m); return hipfail(e, "mix channel plan tables"); }
+    m->modem.recs = m->pair.recs = reinterpret_cast<const nrldpc::MixChanRec*>(m->blob + o_rec);
+    m->modem.prefix = reinterpret_cast<const int32_t*>(m->blob + o_mp);
+    m->pair.prefix = reinterpret_cast<const int32_t*>(m->blob + o_pp);
+    *out = m;
+    return NRLDPC_OK;
+    NRLDPC_API_END
+}
+
+int nrldpc_mix_chan_awgn_llr_dev(nrldpc_mix_chan_handle m, const uint8_t* d_g, const nrldpc_mix_chan_point* d_pt, float* d_g_tilde, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if (m->size_g > 0 && (!d_g || !d_g_tilde)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->pair.n_wg == 0) return NRLDPC_OK;
+    if (!d_pt) return fail(NRLDPC_ERR_ARG, "null operating points");
+    nrldpc::MixChanLlrLaunch a; // (a launch block of the call's own: calls in flight on several streams share the plan, never a launch block)
+    a.t = m->pair; a.pt = d_pt; a.g = d_g; a.llr = d_g_tilde;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_chan_awgn_llr(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix channel kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_chan_modulate_dev(nrldpc_mix_chan_handle m, const uint8_t* d_g, float* d_tx, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if (m->size_g > 0 && (!d_g || !d_tx)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->modem.n_wg == 0) return NRLDPC_OK;
+    nrldpc::MixChanModLaunch a;
+    a.t = m->modem; a.g = d_g; a.tx = d_tx;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_chan_modulate(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix mapper kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_chan_awgn_dev(nrldpc_mix_chan_handle m, const float* d_tx, const nrldpc_mix_chan_point* d_pt, const float* d_variance,
+                             float* d_rx, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if (m->size_sym > 0 && (!d_tx || !d_rx)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->pair.n_wg == 0) return NRLDPC_OK;
+    if (!d_pt) return fail(NRLDPC_ERR_ARG, "null operating points"); // (seed and first_symbol are read with the array too)
+    nrldpc::MixChanAwgnLaunch a;
+    a.t = m->pair; a.pt = d_pt; a.tx = d_tx; a.var = d_variance; a.rx = d_rx;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_chan_awgn(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix AWGN kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_chan_demodulate_dev(nrldpc_mix_chan_handle m, const float* d_rx, int32_t method, const nrldpc_mix_chan_point* d_pt,
+                                   const float* d_variance, void* d_out, int32_t out_dtype, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if (method != NRLDPC_DEMOD_LLR && method != NRLDPC_DEMOD_APPROX_LLR && method != NRLDPC_DEMOD_HARD)
+        return fail(NRLDPC_ERR_UNSUPPORTED, "unknown decision method");
+    const bool hard = method == NRLDPC_DEMOD_HARD;
+    if (!hard && out_dtype != NRLDPC_LLR_F32 && out_dtype != NRLDPC_LLR_F16) return fail(NRLDPC_ERR_UNSUPPORTED, "out_dtype must be f32 or f16");
+    if (m->size_sym > 0 && (!d_rx || !d_out)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->modem.n_wg == 0) return NRLDPC_OK;
+    if (!hard && !d_variance && !d_pt) return fail(NRLDPC_ERR_ARG, "null operating points");
+    nrldpc::MixChanDemodLaunch a;
+    a.t = m->modem; a.pt = d_pt; a.rx = d_rx; a.var = d_variance; a.out = d_out; a.method = method; a.out_dtype = out_dtype;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_chan_demodulate(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix demapper kernel launch");
     return NRLDPC_OK;
 }
 

@@ -8,7 +8,7 @@ import copy
 
 import numpy as np
 
-from ._capi import LLR_F16, LLR_F32, MIX_FIELDS, MIX_SKIP_SETTLED, MIX_SKIP_UNSCHEDULED, Codec, MixPlan, MixTxPlan, MultiCall, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, rate_recover_dev, tb_params
+from ._capi import LLR_F16, LLR_F32, MIX_FIELDS, MIX_SKIP_SETTLED, MIX_SKIP_UNSCHEDULED, Codec, MixChanPlan, MixPlan, MixTxPlan, MultiCall, NRLDPCError, UnsupportedParameters, algorithm_code, crc_check_harq_dev, demod_method_code, rate_recover_dev, tb_params
 from .nrldpc import NRLDPC
 
 
@@ -578,3 +578,127 @@ class MixedEncodeChain:
                 self.plan.encode(self.codecs, self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
             self.plan.rate_match(self.cw.data_ptr(), self.g.data_ptr() if self.g.numel() else None, stream=stream)
         return self.g
+
+
+class MixedChannel:
+    """The channel leg for a MIX of configurations, between MixedEncodeChain and MixedDecodeChain: n parameter sets (NRLDPC objects)
+    with n_tb[i] transport blocks each, from the packed rate-matched bits g to the packed LLRs g_tilde, each configuration at its own
+    modulation order, Es/N0, seed and first symbol.  Fused by default -- MixChanPlan.awgn_llr, ONE launch, the symbols never exist in
+    memory -- or, with separate=True, mapper -> noise (in place) -> demapper, one launch each; that route alone offers the decision
+    methods and f16 LLRs.  Both arrays are PACKED in field g of the receive layout: configuration i's segment starts at
+    plan.off[i].g and is exactly the [n_tb][G] array of the single-configuration calls; symbols ("sym": [n_sym][2] floats) and
+    per-symbol values ("var": [n_sym]) start at plan.sym_off[i] symbols; views() / pack() convert.  The n operating-point records go
+    up with one non-blocking copy from a pinned tensor per step."""
+
+    _SHAPES = {"g": lambda t, n: (n, t.G), "sym": lambda t, n: (n * t.G // t.Q_m, 2), "var": lambda t, n: (n * t.G // t.Q_m,)}
+
+    def __init__(self, params, n_tb, device_id=0):
+        import torch
+        self.torch = torch
+        params = list(params)
+        for p in params:
+            p.validate()
+        self.params, self.n_tb = params, [int(x) for x in n_tb]
+        self.dev = torch.device("cuda", device_id)
+        self.device_id = device_id
+        self.g_tilde = self.tx = self._pt = self._pt_host = self._pt_done = None
+        self._out = {}
+        self.plan = MixChanPlan(params, self.n_tb, device_id=device_id)
+        try:
+            if any(self.n_tb):
+                # the chain's own packed arrays, allocated once at the plan's totals (gaps stay zero: the kernels never touch them)
+                self.g_tilde = torch.zeros(self.plan.totals()["g"], dtype=torch.float32, device=self.dev)
+                self._pt = torch.zeros(32 * self.plan.n, dtype=torch.uint8, device=self.dev)
+                self._pt_host = torch.zeros(32 * self.plan.n, dtype=torch.uint8).pin_memory()
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        if getattr(self, "plan", None) is not None:
+            self.plan.close()
+
+    def _offset(self, i, field):
+        return self.plan.off[i].g if field == "g" else self.plan.sym_off[i] * (2 if field == "sym" else 1)
+
+    def _total(self, field):
+        tot = self.plan.totals()
+        return tot["g"] if field == "g" else tot["sym"] * (2 if field == "sym" else 1)
+
+    def views(self, packed, field):
+        """The per-configuration views of a packed tensor: field is one of "g" (bits, LLRs or hard bits: [n_tb][G]), "sym" (a float
+        tensor of 2 * totals()["sym"] elements: [n_sym][2]) and "var" (one value per symbol: [n_sym])."""
+        if field not in self._SHAPES:
+            raise NRLDPCError("unknown field %r (one of %s)" % (field, ", ".join(self._SHAPES)))
+        flat = packed.reshape(-1)
+        if flat.numel() < self._total(field):
+            raise NRLDPCError("the packed %s array should hold at least %d elements." % (field, self._total(field)))
+        out = []
+        for i, t in enumerate(self.plan.params):
+            shape = self._SHAPES[field](t, self.n_tb[i])
+            o = self._offset(i, field)
+            out.append(flat[o: o + int(np.prod(shape, dtype=np.int64))].view(shape))
+        return out
+
+    def pack(self, tensors, field):
+        """A packed tensor (gaps zero, the tensors' dtype) from one tensor per configuration, each of the shape views() gives for `field`."""
+        tensors = list(tensors)
+        if len(tensors) != len(self.params):
+            raise NRLDPCError("one tensor per configuration expected (%d), got %d." % (len(self.params), len(tensors)))
+        if field not in self._SHAPES:
+            raise NRLDPCError("unknown field %r (one of %s)" % (field, ", ".join(self._SHAPES)))
+        dtype = tensors[0].dtype if tensors else self.torch.uint8
+        packed = self.torch.zeros(self._total(field), dtype=dtype, device=self.dev)
+        for v, x in zip(self.views(packed, field), tensors):
+            if tuple(x.shape) != tuple(v.shape) or x.dtype != dtype:
+                raise NRLDPCError("a %s tensor of shape %s expected for field %r, got %s %s." % (dtype, tuple(v.shape), field, tuple(x.shape), x.dtype))
+            v.copy_(x)
+        return packed
+
+    def step(self, g_packed, EsN0_dB, seed, first_symbol=0, separate=False, method="llr", llr_dtype=None):
+        """g_packed: the packed rate-matched bits, a contiguous 1-D uint8 device tensor of at least plan.totals()["g"] elements
+        (MixedEncodeChain.step's result); only bit 0 of a byte is read.  EsN0_dB, seed, first_symbol: one value per configuration, or
+        scalars, which broadcast (first_symbol: the global index of the configuration's first symbol -- noise is a function of
+        (seed, global symbol index) alone).  Returns the packed g_tilde in the layout of MixedDecodeChain's "g" field: the chain's own
+        device array, valid until the next step (clone what must live longer) -- f32 LLRs, or with separate=True what `method`
+        ("llr", "approx", "hard"; names as in demod_method_code) and llr_dtype (torch.float32 / torch.float16) ask for; "hard" gives
+        uint8 bits."""
+        torch, g = self.torch, g_packed
+        code = demod_method_code(method)
+        if llr_dtype not in (None, torch.float32, torch.float16):
+            raise NRLDPCError("llr_dtype should be torch.float32 or torch.float16, got %s." % (llr_dtype,))
+        if not separate and (code != demod_method_code("llr") or llr_dtype not in (None, torch.float32)):
+            raise NRLDPCError("the fused route gives exact f32 LLRs; decision methods and f16 need separate=True.")
+        pts = self.plan.points(EsN0_dB, seed, first_symbol)
+        need = self.plan.totals()["g"]
+        if not isinstance(g, torch.Tensor) or g.dim() != 1 or g.dtype != torch.uint8 or not g.is_contiguous():
+            raise NRLDPCError("g should be a contiguous 1-D uint8 device tensor of at least %d elements." % need)
+        if not g.is_cuda or g.device != self.dev:
+            raise NRLDPCError("g lives on %s, this chain on %s." % (g.device, self.dev))
+        if g.numel() < need:
+            raise NRLDPCError("g should be a contiguous 1-D uint8 device tensor of at least %d elements, got %d." % (need, g.numel()))
+        hard = code == demod_method_code("hard")
+        out_dtype = torch.uint8 if hard else (llr_dtype or torch.float32)
+        if self.g_tilde is None:  # the empty plan: nothing to do
+            return torch.zeros(0, dtype=out_dtype, device=self.dev)
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            if self._pt_done is not None:
+                self._pt_done.synchronize()  # the pinned records of the previous step have gone up
+            self._pt_host.copy_(torch.from_numpy(np.frombuffer(pts, np.uint8)[:32 * self.plan.n]))
+            self._pt.copy_(self._pt_host, non_blocking=True)
+            self._pt_done = torch.cuda.Event()
+            self._pt_done.record()
+            if not separate:
+                self.plan.awgn_llr(g.data_ptr(), self._pt.data_ptr(), self.g_tilde.data_ptr(), stream=stream)
+                return self.g_tilde
+            if self.tx is None:
+                self.tx = torch.zeros(2 * self.plan.totals()["sym"], dtype=torch.float32, device=self.dev)
+            out = self.g_tilde if out_dtype == torch.float32 else self._out.get(out_dtype)
+            if out is None:
+                out = self._out[out_dtype] = torch.zeros(need, dtype=out_dtype, device=self.dev)
+            self.plan.modulate(g.data_ptr(), self.tx.data_ptr(), stream=stream)
+            self.plan.awgn(self.tx.data_ptr(), self._pt.data_ptr(), self.tx.data_ptr(), stream=stream)
+            self.plan.demodulate(self.tx.data_ptr(), self._pt.data_ptr(), out.data_ptr(), method=method,
+                                 out_dtype=LLR_F16 if out_dtype == torch.float16 else LLR_F32, stream=stream)
+        return out
