@@ -69,7 +69,8 @@ def test_hard_output_kernels_iteration_by_iteration(pkg, orc, bg):
         for iters in (1, 2, 3):
             run_case(pkg, orc, rng, 2, 208, 5, -1.0, iters, nl=21, et=False, app=False)
         run_case(pkg, orc, rng, 2, 208, 5, 1.0, 12, nl=21, et=True, app=False)
-    if bg == 2:  # ... and NRLDPC_Z64P_NL_LIST (BASELINE configs[0]: Z = 20, 12 rows), packed geometry
+    if bg == 2:  # ... and BASELINE configs[0] (Z = 20, 12 rows): the interleaved entry (2, 20, 12, mode 5) takes these calls, fixed and
+        # stop, before NRLDPC_Z64P_NL_LIST is looked at -- that list's packed unit is not reached (tests/decode_cases.py)
         for iters in (1, 2, 3):
             run_case(pkg, orc, rng, 2, 20, 37, 1.0, iters, nl=12, et=False, app=False)
         run_case(pkg, orc, rng, 2, 20, 37, 3.0, 12, nl=12, et=True, app=False)
@@ -98,8 +99,12 @@ def _waterfall_esn0(bg, nl):
     return float(np.interp(nl, [p[0] for p in pts], [p[1] for p in pts]))
 
 
-# every kernel family a hard-output call with pruned rows can land on: split form (block geometry; 384 and 288 with dual rows),
-# one-thread-per-row pipelined form (144, 192, 320, 352; BG2 384), packed geometry (8 ... 80), run-time-Z kernel (the rest)
+# every kernel family a hard-output call with pruned rows can land on (tests/decode_cases.py names the kernel of each call, and
+# profiles/decode_routes.json holds that against a kernel trace): split form (block geometry: 208, 256, BG1 288 and 384; BG2 64, 96,
+# 128 with the parity stop), one-thread-per-row pipelined form (144, 320; BG2 192, 288, 352, 384; BG1 192 with the parity stop), the
+# interleaved block geometry (8 ... 128 at fixed iterations, and with the parity stop where the entry's mode has bit 4), packed
+# geometry (BG1 352; BG1 20 with the parity stop), BG2's packed general kernel (BG2 56 with the parity stop).  No size of this
+# grid reaches the run-time-Z kernel without soft output
 RT_GRID_Z = (8, 20, 32, 56, 64, 80, 96, 128, 144, 192, 208, 256, 288, 320, 352, 384)
 RT_GRID_NL = (4, 5, 8, 13, 17, 24, 30)
 
@@ -408,7 +413,10 @@ def test_device_pointer_entry_and_timing(pkg, orc):
 @pytest.mark.parametrize("bg,Z,dt", [(1, 384, np.float16), (2, 256, np.float32), (1, 320, np.float16), (1, 240, np.float16), (2, 104, np.float32)])
 def test_unaligned_device_pointers(pkg, orc, bg, Z, dt):
     """The compile-time-Z kernels move LLRs and hard bits in 8/16-byte and 4-byte pieces when the caller's
-    pointers allow it; pointers at odd element offsets must take the narrow path and give the same answer."""
+    pointers allow it; pointers at odd element offsets must take the narrow path and give the same answer.
+    (BG2 Z = 104 at fixed iterations runs the interleaved entry (2, 104, 2, mode 1), a kernel without pointer branches;
+    tests/test_decode_dev_contract_gpu.py runs every pair wide / dword, narrow / byte and wide / byte, and the full cross of the
+    two branches at a small and a large size of each form.)"""
     import torch
     rng = np.random.default_rng(Z)
     kb, B = BG_DIMS[bg][2], 9
