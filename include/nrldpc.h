@@ -724,7 +724,8 @@ int nrldpc_awgn_dev(const float* d_tx /* [n_sym][2] */, int64_t n_sym,
  *   method or a dtype other than F32 / F16 with NRLDPC_ERR_UNSUPPORTED and the single calls' texts.
  *
  * Out of scope: pool variants, the MEX gateway, a mixed payload draw, f16 output of the fused stage, a fused form with per-symbol
- *   variance.  Measurements against the loop of single calls: DESIGN.md section 4.20. */
+ *   variance.  (Of these, a mixed payload draw has been supplied since: nrldpc_mix_tx_payload_dev, in the Monte-Carlo block below.)
+ *   Measurements against the loop of single calls: DESIGN.md section 4.20. */
 typedef struct nrldpc_mix_chan* nrldpc_mix_chan_handle;
 
 typedef struct nrldpc_mix_chan_point {
@@ -748,6 +749,51 @@ int nrldpc_mix_chan_awgn_dev(nrldpc_mix_chan_handle m, const float* d_tx, const 
                              const float* d_variance /* nullable, packed symbol layout */, float* d_rx /* may equal d_tx */, void* stream);
 int nrldpc_mix_chan_demodulate_dev(nrldpc_mix_chan_handle m, const float* d_rx, int32_t method, const nrldpc_mix_chan_point* d_pt,
                                    const float* d_variance /* nullable */, void* d_out /* field g */, int32_t out_dtype, void* stream);
+
+/* ---- mixed transport-block batches, the Monte-Carlo loop's own two stages: payload draw and outcome latch ----------------------------
+ * What plot_BLER_vs_SNR.m:118-137 does around the encoder, the channel and the decoder, for every configuration of a mix at once: the
+ * payload draw (nrldpc_payload_bits_dev per configuration, in ONE launch) and the per-block bookkeeping of the HARQ loop -- latch a_hat
+ * on the first attempt whose transport-block CRC holds, OR the acknowledgements, compare with the payload, count who still
+ * retransmits -- which the single-configuration harness writes as tensor expressions.  Both calls hang off the TRANSMIT plan
+ * (nrldpc_mix_tx_handle), which already owns the payload layout a_off, A_i, n_tb[i] and the receive layout's offsets; the plan's
+ * tables grow by one 40-byte record per configuration and one prefix table.  Added without a revision bump (NRLDPC_ABI_VERSION stays
+ * 6): a binding finds the functions by symbol.  With the transmit, channel and receive stages above, a Monte-Carlo point on a mix is a
+ * number of launches that does not depend on n (harness.simulate_point_mixed).
+ *
+ * nrldpc_mix_tx_payload_dev.  d_draw: a caller-owned DEVICE array of n 16-byte records, read on the device and not validated there (a
+ *   per-call operating point, as nrldpc_mix_chan_point is).  Semantics, by equality: segment i of d_a is bit for bit what
+ *     nrldpc_payload_bits_dev(d_draw[i].seed, d_draw[i].first_block, n_tb[i], A_i, d_a + a_off[i], stream)
+ *   leaves, first_block >= 2^32 included.  One launch whatever n; gap bytes are never written; any byte address of d_a is served (a
+ *   chunk of four bits is one 4-byte store where it is whole and its real address is a multiple of four, a byte loop otherwise -- the
+ *   rule, and the hash, are one shared copy with the single kernel: csrc/nrldpc_payload_bits.h).
+ *
+ * nrldpc_mix_tx_outcome_dev.  d_a, d_a_hat: the packed payload layout (a_off); d_b_hat: field b_hat; d_ok, d_done, d_good: field tb
+ *   (d_ok is what the CRC stage wrote: int32; d_done and d_good are bytes).  With j = off[i].tb + t the packed index of transport block
+ *   t of configuration i:
+ *     was = first ? 0 : d_done[j] != 0;   now = d_ok[j] != 0;
+ *     if (now && !was)  the A_i bytes at d_a_hat + a_off[i] + t*A_i become the first A_i bytes of the b_hat row at off[i].b_hat + t*B_i;
+ *     d_done[j] = was || now;
+ *     d_good[j] = d_done[j] && the a_hat row equals the a row byte for byte;
+ *     d_left[i] = the number of t < n_tb[i] with d_done == 0 after the call (0 for an empty configuration); nullable.
+ *   A block with neither `was` nor `now` has none of its rows read or written.  With first != 0 the old contents of d_done and d_a_hat
+ *   are never read: stale bytes there reach nothing, and a new batch costs no memset pass (as d_new in the HARQ stages).  Exactly
+ *   harness.simulate_point_device's bookkeeping per transport block.  Integers only, one writer per byte, no atomics; d_left is summed
+ *   in block order by one wave per configuration in a second small launch: at most two launches whatever n, one when d_left is null.
+ *
+ * Both calls only enqueue (no allocation, copy or synchronisation); calls in flight on several streams may share the plan.
+ * Refusals, all before any device call: a null plan, a null base pointer of a non-empty array, a null d_draw with a non-empty plan ->
+ *   NRLDPC_ERR_ARG.  The empty plan returns NRLDPC_OK without a launch and writes nothing, d_left included.
+ * Out of scope: pool and multi-GPU variants, the MEX gateway.  Measurements: DESIGN.md section 4.21. */
+typedef struct nrldpc_mix_draw {
+    uint64_t seed, first_block;   /* splitmix64 seed; global index of the configuration's transport block 0 */
+} nrldpc_mix_draw;                /* sizeof == 16 (the library static_asserts it) */
+
+int nrldpc_mix_tx_payload_dev(nrldpc_mix_tx_handle m, const nrldpc_mix_draw* d_draw /* [n], device */,
+                              uint8_t* d_a /* packed a layout */, void* stream);
+int nrldpc_mix_tx_outcome_dev(nrldpc_mix_tx_handle m, const uint8_t* d_a, const uint8_t* d_b_hat /* field b_hat */,
+                              const int32_t* d_ok /* field tb */, int32_t first,
+                              uint8_t* d_a_hat /* in/out, a layout */, uint8_t* d_done /* in/out, tb layout */,
+                              uint8_t* d_good /* out, tb layout */, int32_t* d_left /* out, [n], nullable */, void* stream);
 
 /* Kernel timing: when enabled, every *_dev / host call records HIP events around its kernel on the
  * launch stream; nrldpc_last_kernel_ms synchronises on the stop event and returns the duration. */

@@ -114,6 +114,12 @@ class MixChanPoint(C.Structure):
     _fields_ = [("variance", C.c_float), ("sigma", C.c_float), ("inv_n0", C.c_float), ("reserved", C.c_uint32),
                 ("seed", C.c_uint64), ("first_symbol", C.c_uint64)]
 
+class MixDraw(C.Structure):
+    """nrldpc_mix_draw: the payload draw of one configuration of a transmit plan (16 bytes; a device array of n of them goes to
+    nrldpc_mix_tx_payload_dev): the splitmix64 seed and the global index of the configuration's transport block 0."""
+    _fields_ = [("seed", C.c_uint64), ("first_block", C.c_uint64)]
+
+
 EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_dev", "nrldpc_crc_check_harq_dev", "nrldpc_crc_attach_dev", "nrldpc_rate_match_dev", "nrldpc_create", "nrldpc_destroy", "nrldpc_get_dims", "nrldpc_decode", "nrldpc_decode_dev",
            "nrldpc_decode_multi_dev", "nrldpc_quantise_llr", "nrldpc_encode", "nrldpc_encode_dev", "nrldpc_set_timing", "nrldpc_last_kernel_ms",
            "nrldpc_set_index", "nrldpc_lifting_size", "nrldpc_default_rule", "nrldpc_strerror", "nrldpc_last_error",
@@ -129,7 +135,8 @@ EXPORTS = ["nrldpc_awgn_llr_dev", "nrldpc_rate_recover_dev",  "nrldpc_crc_check_
            "nrldpc_mix_tx_layout", "nrldpc_mix_tx_create", "nrldpc_mix_tx_destroy", "nrldpc_mix_tx_crc_attach_dev", "nrldpc_mix_tx_encode_dev",
            "nrldpc_mix_tx_rate_match_dev", "nrldpc_mix_tx_encode_all_dev",
            "nrldpc_mix_chan_layout", "nrldpc_mix_chan_point_set", "nrldpc_mix_chan_create", "nrldpc_mix_chan_destroy",
-           "nrldpc_mix_chan_awgn_llr_dev", "nrldpc_mix_chan_modulate_dev", "nrldpc_mix_chan_awgn_dev", "nrldpc_mix_chan_demodulate_dev"]
+           "nrldpc_mix_chan_awgn_llr_dev", "nrldpc_mix_chan_modulate_dev", "nrldpc_mix_chan_awgn_dev", "nrldpc_mix_chan_demodulate_dev",
+           "nrldpc_mix_tx_payload_dev", "nrldpc_mix_tx_outcome_dev"]
 
 _lib = None
 
@@ -229,6 +236,9 @@ def load():
         L.nrldpc_mix_tx_rate_match_dev.argtypes = [vp, vp, vp, vp]
     if hasattr(L, "nrldpc_mix_tx_encode_all_dev"):  # the encode stage in one launch, found by symbol like the rest
         L.nrldpc_mix_tx_encode_all_dev.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "nrldpc_mix_tx_payload_dev"):  # the Monte-Carlo loop's payload draw and outcome latch, found by symbol like the rest
+        L.nrldpc_mix_tx_payload_dev.argtypes = [vp, vp, vp, vp]
+        L.nrldpc_mix_tx_outcome_dev.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     if hasattr(L, "nrldpc_mix_chan_create"):  # the channel leg of the mixed batches, found by symbol like the rest
         L.nrldpc_mix_chan_layout.argtypes = [i32, C.POINTER(TbParams), C.POINTER(i32), C.POINTER(C.c_int64)]
         L.nrldpc_mix_chan_point_set.argtypes = [C.c_float, C.c_uint64, C.c_uint64, C.POINTER(MixChanPoint)]
@@ -800,6 +810,43 @@ class MixTxPlan:
     def rate_match(self, d_cw, d_g, stream=0):
         """nrldpc_mix_tx_rate_match_dev on raw device addresses of the packed arrays."""
         check(self._lib.nrldpc_mix_tx_rate_match_dev(self._h, _ptr(d_cw), _ptr(d_g), C.c_void_p(stream)))
+
+    def _mc_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise NRLDPCError("%s has no %s: the Monte-Carlo stages of mixed transport-block batches need a library built from this "
+                              "tree (NRLDPC_LIB selects an older one?)" % (lib_path(), name))
+        return fn
+
+    def draws(self, seed, first_block=0):
+        """The n nrldpc_mix_draw records of one payload() call as a ctypes array (host only), as MixChanPlan.points makes the channel's:
+        seed and first_block are sequences of n values or scalars, which broadcast.  Copy the array to the device (16 * n bytes;
+        np.frombuffer(d, np.uint8) views it -- one non-blocking copy from a pinned tensor) and hand its address to payload()."""
+        def spread(x, what):
+            xs = list(x) if hasattr(x, "__len__") else [x] * self.n
+            if len(xs) != self.n:
+                raise NRLDPCError("one %s per configuration expected (%d), got %d." % (what, self.n, len(xs)))
+            return xs
+        sd, fb = spread(seed, "seed"), spread(first_block, "first_block")
+        d = (MixDraw * max(self.n, 1))()
+        for i in range(self.n):
+            if not 0 <= int(fb[i]) < 1 << 64:
+                raise NRLDPCError("first_block should lie in [0, 2^64)")
+            d[i].seed, d[i].first_block = int(sd[i]) % (1 << 64), int(fb[i])
+        return d
+
+    def payload(self, d_draw, d_a, stream=0):
+        """nrldpc_mix_tx_payload_dev on raw device addresses: the payload draw of every configuration in ONE launch; segment i of the
+        packed a becomes what payload_bits_dev(seed_i, first_block_i, n_tb[i], A_i) leaves."""
+        check(self._mc_fn("nrldpc_mix_tx_payload_dev")(self._h, _ptr(d_draw), _ptr(d_a), C.c_void_p(stream)))
+
+    def outcome(self, d_a, d_b_hat, d_ok, first, d_a_hat, d_done, d_good, d_left=None, stream=0):
+        """nrldpc_mix_tx_outcome_dev on raw device addresses: the HARQ loop's bookkeeping of one attempt for every transport block of
+        the mix -- a_hat (packed a layout) latched from b_hat where the block's CRC holds for the first time, done |= ok, good = done
+        and a_hat == a (bytes, packed tb layout), d_left[i] (int32 [n], optional) = blocks of configuration i not yet done.  first:
+        the batch's first attempt -- the old contents of d_done and d_a_hat are not read."""
+        check(self._mc_fn("nrldpc_mix_tx_outcome_dev")(self._h, _ptr(d_a), _ptr(d_b_hat), _ptr(d_ok), 1 if first else 0, _ptr(d_a_hat),
+                                                      _ptr(d_done), _ptr(d_good), _ptr(d_left), C.c_void_p(stream)))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -29,7 +29,7 @@ NOPAIR = bool(os.environ.get("NRLDPC_BUILD_NOPAIR"))
 LIB = os.environ.get("NRLDPC_LIB") or os.path.join(HERE, "libnrldpc_hip_ab.so" if AB else "libnrldpc_hip_allmodes.so" if ALLMODES else "libnrldpc_hip_x.so" if XFLAGS else "libnrldpc_hip_nopair.so" if NOPAIR else "libnrldpc_hip.so")  # env override: kernel experiments
 OBJDIR = os.path.join(HERE, "build_ab" if AB else "build_allmodes" if ALLMODES else "build_x" if XFLAGS else "build_nopair" if NOPAIR else "build")
 SOURCES = ["nrldpc_decode.hip", "nrldpc_encode.hip", "nrldpc_ratematch.hip", "nrldpc_crc.hip", "nrldpc_channel.hip",
-           "nrldpc_expand.hip", "nrldpc_decode_bp.hip", "nrldpc_cwout.hip", "nrldpc_modem.hip", "nrldpc_awgn.hip", "nrldpc_ratematch_ex.hip", "nrldpc_mix.hip", "nrldpc_mix_skip.hip", "nrldpc_mix_tx.hip", "nrldpc_mix_tx_enc.hip", "nrldpc_mix_modem.hip", "nrldpc_mix_chan.hip", "nrldpc_capi.hip", "nrldpc_host_quant.cpp"]  # .cpp: host-only C++ (no device pass)
+           "nrldpc_expand.hip", "nrldpc_decode_bp.hip", "nrldpc_cwout.hip", "nrldpc_modem.hip", "nrldpc_awgn.hip", "nrldpc_ratematch_ex.hip", "nrldpc_mix.hip", "nrldpc_mix_skip.hip", "nrldpc_mix_tx.hip", "nrldpc_mix_tx_enc.hip", "nrldpc_mix_modem.hip", "nrldpc_mix_chan.hip", "nrldpc_mix_mc.hip", "nrldpc_capi.hip", "nrldpc_host_quant.cpp"]  # .cpp: host-only C++ (no device pass)
 Z64_SOURCE = "nrldpc_decode_z64_inst.hip"
 Z64P_SOURCE = "nrldpc_decode_z64p_inst.hip"
 # the same instantiation with the split form's two-smallest search over pairs of edges (nrldpc_decode_z64_pair.h)
@@ -65,7 +65,7 @@ Z64_NL = [(1, 384, 5), (1, 384, 13), (1, 384, 24), (2, 384, 32), (2, 384, 22), (
 # (BG, Z) whose units -- the Z64_NL units of the same pair included: they share the code -- compile from Z64Q_SOURCE.  A size joins only with
 # a timed A/B of its own against the NRLDPC_BUILD_NOPAIR library (profiles/r07_pair_search_ab.txt)
 Z64_PAIR = [(1, 384)]
-HEADERS = [Z64Q_HEADER, "nrldpc_kernels.h", "nrldpc_dispatch_lists.h", "nrldpc_sched.h", "nrldpc_device.h", "nrldpc_decode_z64.h", "nrldpc_decode_z64s.h", "nrldpc_decode_z64p.h", "nrldpc_wave.h", "nrldpc_host_quant.h", "nrldpc_hostpath.h", "nrldpc_bp.h", "nrldpc_cwout.h", "nrldpc_modem.h", "nrldpc_noise.h", "nrldpc_ratematch_ex.h", "nrldpc_mix.h", "nrldpc_mix_skip.h", "nrldpc_mix_tx.h", "nrldpc_rm_core.h", "nrldpc_crc_wave.h", "nrldpc_mix_chan.h", "nrldpc_modem_sym.h", "nrldpc_awgn_sym.h", "nrldpc_channel_sym.h"]
+HEADERS = [Z64Q_HEADER, "nrldpc_kernels.h", "nrldpc_dispatch_lists.h", "nrldpc_sched.h", "nrldpc_device.h", "nrldpc_decode_z64.h", "nrldpc_decode_z64s.h", "nrldpc_decode_z64p.h", "nrldpc_wave.h", "nrldpc_host_quant.h", "nrldpc_hostpath.h", "nrldpc_bp.h", "nrldpc_cwout.h", "nrldpc_modem.h", "nrldpc_noise.h", "nrldpc_ratematch_ex.h", "nrldpc_mix.h", "nrldpc_mix_skip.h", "nrldpc_mix_tx.h", "nrldpc_rm_core.h", "nrldpc_crc_wave.h", "nrldpc_mix_chan.h", "nrldpc_modem_sym.h", "nrldpc_awgn_sym.h", "nrldpc_channel_sym.h", "nrldpc_mix_mc.h", "nrldpc_payload_bits.h"]
 # -mllvm -enable-post-misched=false: LLVM's post-register-allocation machine scheduler off.  The decoder loops are VALU-issue bound and
 # hand-ordered (pinned read batches, s_setprio windows, launder() fences); the pre-RA scheduler keeps that order, the post-RA pass
 # reshuffles it for latencies the other waves of the CU already hide.  Measured on the MI355X over every lifting size, whole library

@@ -41,6 +41,7 @@
 #include "nrldpc_mix_skip.h"
 #include "nrldpc_mix_tx.h"
 #include "nrldpc_mix_chan.h"
+#include "nrldpc_mix_mc.h"
 #include "nrldpc_rm_core.h"
 
 static_assert(sizeof(nrldpc_cw_out) == 32, "nrldpc_cw_out: the size include/nrldpc.h states");
@@ -2487,6 +2488,8 @@ struct nrldpc_mix_tx {
     nrldpc::MixTxCrcLaunch crc{};
     nrldpc::MixTxRmLaunch rm{};
     nrldpc::MixTxEncLaunch enc{};        // nrldpc_mix_tx_encode_all_dev
+    nrldpc::MixMcPayLaunch pay{};        // nrldpc_mix_tx_payload_dev
+    nrldpc::MixMcOutLaunch outc{};       // nrldpc_mix_tx_outcome_dev (its transport-block prefix is the attach stage's)
 };
 
 namespace {
@@ -2504,6 +2507,9 @@ struct MixTxHost {
     std::vector<int32_t> enc_prefix, enc_first; // enc_first: the first configuration of each distinct (BG, Z_c)
     std::vector<uint8_t> enc_tab;
     int64_t enc_lds = 0;
+    // the Monte-Carlo stages (nrldpc_mix_mc.h): records and the payload grid's workgroup prefix
+    std::vector<nrldpc::MixMcRec> mc;
+    std::vector<int32_t> pay_prefix;
 };
 
 // the encoder record of one non-empty configuration: sizes, waves per codeword, and -- once per distinct (BG, Z_c) -- the solve order
@@ -2549,8 +2555,9 @@ int mix_tx_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool
     m.rm_prefix.assign((size_t)n + 1, 0);
     m.tb_prefix.assign((size_t)n + 1, 0);
     m.enc_prefix.assign((size_t)n + 1, 0);
-    if (tables) { m.rm.resize(n); m.crc.resize(n); m.enc.resize(n); }
-    int64_t wg = 0, wg_rx = 0, tbs = 0, wg_enc = 0;
+    m.pay_prefix.assign((size_t)n + 1, 0);
+    if (tables) { m.rm.resize(n); m.crc.resize(n); m.enc.resize(n); m.mc.resize(n); }
+    int64_t wg = 0, wg_rx = 0, tbs = 0, wg_enc = 0, wg_pay = 0;
     for (int i = 0; i < n; ++i) {
         const nrldpc_tb_params* q = p + i;
         nrldpc::RmExArgs blocks;
@@ -2576,7 +2583,9 @@ int mix_tx_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool
         const int64_t n_cw = (int64_t)n_tb[i] * q->C; // (below 2^31 once wg_rx is: a code block takes a receive workgroup at least)
         const int32_t nwc = nrldpc::mix_tx_enc_nwc(q->bg, q->Z), per_enc = nrldpc::mix_tx_enc_per_wg(nwc);
         wg_enc += (n_cw + per_enc - 1) / per_enc;
-        if (wg > INT32_MAX || wg_rx > INT32_MAX || tbs > INT32_MAX || wg_enc > INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
+        wg_pay += nrldpc::mix_mc_pay_wgs(n_tb[i], q->A); // (A/1024 workgroups a block: fewer than wg_rx, so no plan is refused that was not)
+        if (wg > INT32_MAX || wg_rx > INT32_MAX || tbs > INT32_MAX || wg_enc > INT32_MAX || wg_pay > INT32_MAX) return fail(NRLDPC_ERR_UNSUPPORTED, "the mix is too large for one launch");
+        m.pay_prefix[i + 1] = (int32_t)wg_pay;
         m.rm_prefix[i + 1] = (int32_t)wg;
         m.tb_prefix[i + 1] = (int32_t)tbs;
         m.enc_prefix[i + 1] = (int32_t)wg_enc;
@@ -2602,6 +2611,10 @@ int mix_tx_build(int32_t n, const nrldpc_tb_params* p, const int32_t* n_tb, bool
         memset(&en, 0, sizeof en);
         en.c_off = cur[nrldpc::MIX_C_HAT]; en.cw_off = cur[nrldpc::MIX_CW];
         en.n_cw = (int32_t)n_cw;
+        nrldpc::MixMcRec& mc = m.mc[i];
+        memset(&mc, 0, sizeof mc);
+        mc.a_off = m.a_off[i]; mc.b_hat_off = cur[nrldpc::MIX_B_HAT]; mc.tb_off = cur[nrldpc::MIX_TB];
+        mc.n_tb = n_tb[i]; mc.A = q->A; mc.B = q->B;
         if (n_cw > 0) { // (an empty configuration has no workgroup: its record is never read)
             const int rce = mix_tx_enc_fill(q->bg, q->Z, i, m);
             if (rce) return mix_fail_at(rce, i);
@@ -2654,13 +2667,16 @@ int nrldpc_mix_tx_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_
     m->crc.n = n; m->crc.n_tb_total = mh.tb_prefix[n];
     m->crc.k_max = mh.k_max; m->crc.c_max = mh.c_max; m->crc.waves = nrldpc::mix_tx_waves(mh.c_max);
     m->enc.n = n; m->enc.n_wg = mh.enc_prefix[n]; m->enc.lds_bytes = (int32_t)mh.enc_lds;
+    m->pay.n = n; m->pay.n_wg = mh.pay_prefix[n];
+    m->outc.n = n; m->outc.n_tb_total = mh.tb_prefix[n];
     if (empty) { *out = m; return NRLDPC_OK; }
     // one allocation, every table at a multiple of 16 bytes, uploaded synchronously and never written again
     auto pad16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_rm = 0, o_crc = o_rm + pad16(mh.rm.size() * sizeof(nrldpc::MixTxRmRec)), o_rp = o_crc + pad16(mh.crc.size() * sizeof(nrldpc::MixTxCrcRec)),
                  o_tp = o_rp + pad16(mh.rm_prefix.size() * 4), o_e = o_tp + pad16(mh.tb_prefix.size() * 4), o_o = o_e + pad16(mh.e_tab.size() * 4),
                  o_er = o_o + pad16(mh.off_tab.size() * 4), o_ep = o_er + pad16(mh.enc.size() * sizeof(nrldpc::MixTxEncRec)),
-                 o_et = o_ep + pad16(mh.enc_prefix.size() * 4), total = o_et + pad16(mh.enc_tab.size());
+                 o_et = o_ep + pad16(mh.enc_prefix.size() * 4), o_mc = o_et + pad16(mh.enc_tab.size()),
+                 o_pp = o_mc + pad16(mh.mc.size() * sizeof(nrldpc::MixMcRec)), total = o_pp + pad16(mh.pay_prefix.size() * 4);
     std::vector<char> img(total, 0);
     memcpy(img.data() + o_rm, mh.rm.data(), mh.rm.size() * sizeof(nrldpc::MixTxRmRec));
     memcpy(img.data() + o_crc, mh.crc.data(), mh.crc.size() * sizeof(nrldpc::MixTxCrcRec));
@@ -2671,6 +2687,8 @@ int nrldpc_mix_tx_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_
     memcpy(img.data() + o_er, mh.enc.data(), mh.enc.size() * sizeof(nrldpc::MixTxEncRec));
     memcpy(img.data() + o_ep, mh.enc_prefix.data(), mh.enc_prefix.size() * 4);
     memcpy(img.data() + o_et, mh.enc_tab.data(), mh.enc_tab.size());
+    memcpy(img.data() + o_mc, mh.mc.data(), mh.mc.size() * sizeof(nrldpc::MixMcRec));
+    memcpy(img.data() + o_pp, mh.pay_prefix.data(), mh.pay_prefix.size() * 4);
     DeviceScope scope(device_id);
     hipError_t e = scope.err;
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->blob), total);
@@ -2685,6 +2703,9 @@ int nrldpc_mix_tx_create(int32_t n, const nrldpc_tb_params* p, const int32_t* n_
     m->enc.recs = reinterpret_cast<const nrldpc::MixTxEncRec*>(m->blob + o_er);
     m->enc.prefix = reinterpret_cast<const int32_t*>(m->blob + o_ep);
     m->enc.tab = reinterpret_cast<const uint8_t*>(m->blob + o_et);
+    m->pay.recs = m->outc.recs = reinterpret_cast<const nrldpc::MixMcRec*>(m->blob + o_mc);
+    m->pay.prefix = reinterpret_cast<const int32_t*>(m->blob + o_pp);
+    m->outc.tb_prefix = m->crc.prefix;
     *out = m;
     return NRLDPC_OK;
     NRLDPC_API_END
@@ -2748,6 +2769,38 @@ int nrldpc_mix_tx_rate_match_dev(nrldpc_mix_tx_handle m, const uint8_t* d_cw, ui
     if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
     hipError_t e = nrldpc::launch_mix_tx_rate_match(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hipfail(e, "mix rate-matching kernel launch");
+    return NRLDPC_OK;
+}
+
+// ---- the Monte-Carlo loop's own two stages on the transmit plan (kernels: nrldpc_mix_mc.hip, records and mapping: nrldpc_mix_mc.h) ----
+static_assert(sizeof(nrldpc_mix_draw) == 16, "nrldpc_mix_draw: the size include/nrldpc.h states");
+
+int nrldpc_mix_tx_payload_dev(nrldpc_mix_tx_handle m, const nrldpc_mix_draw* d_draw, uint8_t* d_a, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    if (m->size_a > 0 && !d_a) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->pay.n_wg == 0) return NRLDPC_OK;
+    if (!d_draw) return fail(NRLDPC_ERR_ARG, "null draw records");
+    nrldpc::MixMcPayLaunch a = m->pay; // (a copy: calls in flight on several streams share the plan, never a launch block)
+    a.draw = d_draw; a.a = d_a;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_mc_payload(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix payload kernel launch");
+    return NRLDPC_OK;
+}
+
+int nrldpc_mix_tx_outcome_dev(nrldpc_mix_tx_handle m, const uint8_t* d_a, const uint8_t* d_b_hat, const int32_t* d_ok, int32_t first,
+                              uint8_t* d_a_hat, uint8_t* d_done, uint8_t* d_good, int32_t* d_left, void* stream) {
+    if (!m) return fail(NRLDPC_ERR_ARG, "null mix plan");
+    // (a transport block has A >= 1 payload bytes and B > A bytes of b_hat: every array is non-empty exactly when the payload array is)
+    if (m->size_a > 0 && (!d_a || !d_b_hat || !d_ok || !d_a_hat || !d_done || !d_good)) return fail(NRLDPC_ERR_ARG, "null pointer");
+    if (m->outc.n_tb_total == 0) return NRLDPC_OK;
+    nrldpc::MixMcOutLaunch a = m->outc;
+    a.first = first; a.a = d_a; a.b_hat = d_b_hat; a.ok = d_ok; a.a_hat = d_a_hat; a.done = d_done; a.good = d_good; a.left = d_left;
+    DeviceScope scope(m->device_id);
+    if (scope.err != hipSuccess) return hipfail(scope.err, "hipSetDevice");
+    hipError_t e = nrldpc::launch_mix_mc_outcome(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "mix outcome kernel launch");
     return NRLDPC_OK;
 }
 

@@ -275,6 +275,14 @@ class MixedDecodeChain:
             self.c_hat.zero_()
         self._layers_seen = [4] * len(self.params)
 
+    def new_batch(self):
+        """reset() without a memset, for a caller whose next step flags EVERY transport block as new (step(..., new=all ones)): the flags
+        make the kernels treat harq, cb_pass and b_hat as cleared, so only the sticky layer counts are left to forget.  (Not with skip:
+        there ok and c_hat are state that only reset() clears.)"""
+        if self.skip is not None:
+            raise NRLDPCError("new_batch() is reset() without the memsets; with skip set, ok and c_hat are state: call reset().")
+        self._layers_seen = [4] * len(self.params)
+
     def _plan_for(self, rv_id):
         """The plan (and the active layer counts) for a step's redundancy versions: None = the parameter objects' own, one int for
         every configuration, or a sequence of n.  Built on first use from copies of the parameter objects, then cached."""
@@ -481,7 +489,9 @@ class MixedEncodeChain:
     is exactly the array DeviceEncodeChain uses for that configuration; views() / pack() convert.  The packed g is the layout of
     MixedDecodeChain's "g" field for the same (params, n_tb).  One Codec per distinct (BG, Z_c) among the non-empty configurations.
     one_launch_encode=True: the encode stage is MixTxPlan.encode_all -- one launch from the plan's own tables -- and the chain builds
-    no Codec; the result is the same bit for bit.  The default stays the per-configuration loop."""
+    no Codec; the result is the same bit for bit.  The default stays the per-configuration loop.
+    For a Monte-Carlo loop the chain also draws the payload (draw(): one launch) and keeps the loop's per-block bookkeeping against it
+    (outcome(): at most two launches), and step(a, rv_id=) sends a retransmission (harness.simulate_point_mixed)."""
 
     _SHAPES = {"a": lambda t, n: (n, t.A), "c": lambda t, n: (n * t.C, t.K), "cw": lambda t, n: (n * t.C, 2 * t.Z + t.N), "g": lambda t, n: (n, t.G)}
     _OFF = {"c": "c_hat", "cw": "cw", "g": "g"}
@@ -499,7 +509,11 @@ class MixedEncodeChain:
         self._codecs = {}
         self.codecs = []
         self.c = self.cw = self.g = None
+        # the Monte-Carlo stages' arrays (draw() / outcome()), allocated on first use
+        self.a = self.a_hat = self.done = self.good = self.all_new = self.left = self._left_host = self._draw = self._draw_host = self._draw_done = None
         self.plan = MixTxPlan(params, self.n_tb, device_id=device_id)
+        self._own_rv = tuple(int(p.rv_id) for p in params)
+        self._plans = {self._own_rv: self.plan}  # one plan per tuple of redundancy versions (only step(..., rv_id=) adds to it)
         try:
             for p, k in zip(params, self.n_tb):
                 key = (p.BG, p.Z_c)
@@ -520,8 +534,98 @@ class MixedEncodeChain:
         for c in getattr(self, "_codecs", {}).values():
             c.close()
         self._codecs, self.codecs = {}, []
+        for plan in getattr(self, "_plans", {}).values():
+            plan.close()
+        self._plans = {}
         if getattr(self, "plan", None) is not None:
             self.plan.close()
+
+    def _plan_for(self, rv_id):
+        """The plan for a step's redundancy versions, as MixedDecodeChain._plan_for: None = the parameter objects' own, one int for every
+        configuration, or a sequence of n.  rv_id only moves k_0 and no layout field depends on it, so the plans share the chain's
+        packed arrays.  Built on first use from copies of the parameter objects, then cached."""
+        n = len(self.params)
+        if rv_id is None:
+            key = self._own_rv
+        elif isinstance(rv_id, (int, np.integer)):
+            key = (int(rv_id),) * n
+        else:
+            key = tuple(int(x) for x in rv_id)
+            if len(key) != n:
+                raise NRLDPCError("rv_id should be None, one value or one value per configuration (%d), got %d." % (n, len(key)))
+        if key not in self._plans:
+            ps = []
+            for p, rv in zip(self.params, key):
+                q = copy.copy(p)
+                q.rv_id = rv  # (UnsupportedParameters for a value outside 0 ... 3)
+                ps.append(q)
+            plan = MixTxPlan(ps, self.n_tb, device_id=self.device_id)
+            same = plan.a_off == self.plan.a_off and all(getattr(a, f) == getattr(b, f) for a, b in zip(plan.off, self.plan.off) for f in MIX_FIELDS)
+            if not same:
+                plan.close()
+                raise NRLDPCError("the layout of the plan for rv_id %r differs from the chain's: its packed arrays cannot be shared." % (key,))
+            self._plans[key] = plan
+        return self._plans[key]
+
+    def _mc_arrays(self):
+        torch, n = self.torch, len(self.params)
+        if self.a is None:
+            tot_a, tot_tb = self.plan.totals()["a"], self.plan.off[n].tb
+            # zeroed once, so that the gaps read as zero; the kernels never touch a gap and never read done / a_hat on a first attempt
+            self.a = torch.zeros(tot_a, dtype=torch.uint8, device=self.dev)
+            self.a_hat = torch.zeros(tot_a, dtype=torch.uint8, device=self.dev)
+            self.done = torch.zeros(tot_tb, dtype=torch.uint8, device=self.dev)
+            self.good = torch.zeros(tot_tb, dtype=torch.uint8, device=self.dev)
+            self.all_new = torch.ones(tot_tb, dtype=torch.uint8, device=self.dev)  # MixedDecodeChain.step's `new` for a batch's first attempt
+            self.left = torch.zeros(n, dtype=torch.int32, device=self.dev)
+            self._left_host = torch.zeros(n, dtype=torch.int32).pin_memory()
+            self._draw = torch.zeros(16 * n, dtype=torch.uint8, device=self.dev)
+            self._draw_host = torch.zeros(16 * n, dtype=torch.uint8).pin_memory()
+
+    def draw(self, seed, first_block=0):
+        """The payload draw of the Monte-Carlo loop for every configuration in ONE launch (MixTxPlan.payload): configuration i gets the
+        blocks first_block_i ... first_block_i + n_tb[i] - 1 of seed_i (scalars broadcast), bit for bit harness.payload_bits.  The n draw
+        records go up with one non-blocking copy from a pinned tensor.  Returns the packed payload a: the chain's own device array, valid
+        until the next draw() -- what step() takes and outcome() compares with."""
+        torch = self.torch
+        d = self.plan.draws(seed, first_block)
+        if self.g is None:  # the empty plan: nothing to do
+            return torch.zeros(0, dtype=torch.uint8, device=self.dev)
+        with torch.cuda.device(self.dev):
+            self._mc_arrays()
+            if self._draw_done is not None:
+                self._draw_done.synchronize()  # the pinned records of the previous draw have gone up
+            self._draw_host.copy_(torch.from_numpy(np.frombuffer(d, np.uint8)[:16 * self.plan.n]))
+            self._draw.copy_(self._draw_host, non_blocking=True)
+            self._draw_done = torch.cuda.Event()
+            self._draw_done.record()
+            self.plan.payload(self._draw.data_ptr(), self.a.data_ptr(), stream=torch.cuda.current_stream(self.dev).cuda_stream)
+        return self.a
+
+    def outcome(self, b_hat_packed, ok_packed, first, want_left=True):
+        """The HARQ loop's bookkeeping of one attempt (MixTxPlan.outcome) against the payload of the last draw(): b_hat_packed and
+        ok_packed are MixedDecodeChain.step's results for the same (params, n_tb); first = the batch's first attempt (the state of an
+        earlier batch is not read: no memset).  Returns (good, left): good = the chain's packed uint8 device array in the "tb" layout,
+        1 where a block is acknowledged and its latched a_hat equals a; left = per configuration the number of blocks not yet
+        acknowledged, read back to the host (one small copy and the call's one synchronisation), or None with want_left=False."""
+        torch, n = self.torch, len(self.params)
+        if self.g is None:
+            return torch.zeros(0, dtype=torch.uint8, device=self.dev), ([0] * n if want_left else None)
+        if self.a is None:
+            raise NRLDPCError("outcome() compares with the payload of draw(): call draw() first.")
+        need_b, need_tb = self.plan.off[n].b_hat, self.plan.off[n].tb
+        for x, dt, need, what in ((b_hat_packed, torch.uint8, need_b, "b_hat"), (ok_packed, torch.int32, need_tb, "ok")):
+            if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != dt or not x.is_contiguous() or not x.is_cuda or x.device != self.dev or x.numel() < need:
+                raise NRLDPCError("%s should be a contiguous 1-D %s tensor of at least %d elements on %s." % (what, dt, need, self.dev))
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev)
+            self.plan.outcome(self.a.data_ptr(), b_hat_packed.data_ptr(), ok_packed.data_ptr(), first, self.a_hat.data_ptr(), self.done.data_ptr(),
+                              self.good.data_ptr(), self.left.data_ptr() if want_left else None, stream=stream.cuda_stream)
+            if not want_left:
+                return self.good, None
+            self._left_host.copy_(self.left, non_blocking=True)
+            stream.synchronize()
+        return self.good, [int(x) for x in self._left_host.tolist()]
 
     def _offset(self, i, field):
         return self.plan.a_off[i] if field == "a" else getattr(self.plan.off[i], self._OFF[field])
@@ -555,11 +659,14 @@ class MixedEncodeChain:
             v.copy_(x)
         return packed
 
-    def step(self, a_packed):
+    def step(self, a_packed, rv_id=None):
         """a_packed: the packed payload bits, a contiguous 1-D uint8 device tensor of at least plan.totals()["a"] elements
-        (pack(..., "a")); only bit 0 of a byte is read.  Returns g_packed: the chain's own packed uint8 device array of rate-matched
+        (pack(..., "a")); only bit 0 of a byte is read.  rv_id: the redundancy version(s) of this transmission -- None (the parameter
+        objects' own, the chain's plan), one int for every configuration, or a sequence of n (a HARQ retransmission: _plan_for).
+        Returns g_packed: the chain's own packed uint8 device array of rate-matched
         bits, valid until the next step (clone what must live longer); views(g_packed, "g")[i] is configuration i's [n_tb][G]."""
         torch, a = self.torch, a_packed
+        plan = self.plan if rv_id is None else self._plan_for(rv_id)
         need = self.plan.totals()["a"]
         if not isinstance(a, torch.Tensor) or a.dim() != 1 or a.dtype != torch.uint8 or not a.is_contiguous():
             raise NRLDPCError("a should be a contiguous 1-D uint8 device tensor of at least %d elements." % need)
@@ -571,12 +678,12 @@ class MixedEncodeChain:
             return torch.zeros(0, dtype=torch.uint8, device=self.dev)
         with torch.cuda.device(self.dev):
             stream = torch.cuda.current_stream(self.dev).cuda_stream
-            self.plan.crc_attach(a.data_ptr(), self.c.data_ptr(), stream=stream)
+            plan.crc_attach(a.data_ptr(), self.c.data_ptr(), stream=stream)
             if self.one_launch_encode:
-                self.plan.encode_all(self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
+                plan.encode_all(self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
             else:
-                self.plan.encode(self.codecs, self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
-            self.plan.rate_match(self.cw.data_ptr(), self.g.data_ptr() if self.g.numel() else None, stream=stream)
+                plan.encode(self.codecs, self.c.data_ptr(), self.cw.data_ptr(), stream=stream)
+            plan.rate_match(self.cw.data_ptr(), self.g.data_ptr() if self.g.numel() else None, stream=stream)
         return self.g
 
 

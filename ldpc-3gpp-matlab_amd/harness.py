@@ -246,6 +246,54 @@ def simulate_point_device(chains, Q_m, EsN0, rv_id_sequence, batch, seed, first_
     return np.concatenate(out) if out else np.zeros(0, bool)
 
 
+def simulate_point_mixed(enc, chan, dec, EsN0, rv_id_sequence, seed, first_block):
+    """simulate_point_device for a MIX of configurations side by side: one MixedEncodeChain, one MixedChannel and one
+    MixedDecodeChain(I_HARQ=1) over the same (params, n_tb); EsN0, seed and first_block are scalars or one value per configuration.
+    One payload launch (MixedEncodeChain.draw); per attempt the mixed encoder at that redundancy version, the fused mixed channel --
+    configuration i at first_symbol_i = n_rv * ATTEMPT_STRIDE + first_block_i * (G_i / Q_m_i) -- the mixed decoder step, and one outcome
+    launch (MixedEncodeChain.outcome) that latches a_hat, ORs the acknowledgements and counts who still retransmits; that count is the
+    one small read-back per attempt.  Attempt 0 flags every transport block as new for the decoder and as first for the outcome: the
+    per-batch reset() without a memset.  The number of launches does not depend on the number of configurations.
+
+    Returns one boolean outcome array per configuration; array i equals simulate_point_device([(DeviceEncodeChain(p_i),
+    DeviceDecodeChain(p_i, I_HARQ=1, ...))], Q_m_i, EsN0_i, rv_id_sequence, n_tb[i], seed_i, first_block_i) element for element at the
+    same decoder arguments (every mixed stage is bit-equal to its single call).  A configuration whose blocks are all in keeps being
+    stepped while another still retransmits; its outcomes are latched and do not change."""
+    import torch
+    from ._capi import NRLDPCError
+    n = len(enc.params)
+    if not (list(enc.n_tb) == list(chan.n_tb) == list(dec.n_tb)) or not (len(chan.params) == len(dec.params) == n):
+        raise NRLDPCError("the three chains should be built over the same (params, n_tb).")
+    if not dec.I_HARQ:
+        raise NRLDPCError("simulate_point_mixed runs the HARQ loop: the decode chain needs I_HARQ ~= 0.")
+
+    def spread(x, what):
+        xs = list(x) if hasattr(x, "__len__") else [x] * n
+        if len(xs) != n:
+            raise NRLDPCError("one %s per configuration expected (%d), got %d." % (what, n, len(xs)))
+        return xs
+    es, sd, fb = spread(EsN0, "EsN0"), spread(seed, "seed"), spread(first_block, "first_block")
+    if not any(enc.n_tb):
+        return [np.zeros(0, bool) for _ in range(n)]
+    sym = [p.G // p.Q_m for p in enc.params]
+    with torch.cuda.device(enc.dev):
+        a = enc.draw(sd, fb)                                                                   # :118
+        dec.new_batch()                                                                        # :122, with `new` below
+        good = None
+        for n_rv, rv in enumerate(rv_id_sequence):                                             # :124-137
+            g = enc.step(a, rv_id=int(rv))
+            g_tilde = chan.step(g, es, sd, first_symbol=[n_rv * ATTEMPT_STRIDE + int(fb[i]) * sym[i] for i in range(n)])  # :130-132
+            b_hat, ok, _ = dec.step(g_tilde, rv_id=int(rv), new=enc.all_new if n_rv == 0 else None)
+            more = n_rv + 1 < len(rv_id_sequence)
+            good, left = enc.outcome(b_hat, ok, first=n_rv == 0, want_left=more)
+            if more and not any(left):  # nobody retransmits (:136); one synchronisation per attempt
+                break
+        if good is None:  # an empty rv_id_sequence: nothing was sent
+            return [np.zeros(k, bool) for k in enc.n_tb]
+        host = good.cpu().numpy() != 0
+    return [host[enc.plan.off[i].tb: enc.plan.off[i].tb + enc.n_tb[i]].copy() for i in range(n)]
+
+
 def _count_outcomes(outcomes, found_start, errors, blocks, BLER, target_block_errors):
     """The per-block bookkeeping of plot_BLER_vs_SNR.m:139-155 over one batch of outcomes (True = block decoded), in order:
     before the curve has had its first success a failure ends the point with BLER = 1 (:139-141); afterwards blocks and errors
@@ -372,10 +420,115 @@ def plot_BLER_vs_SNR(A=3842, R=1 / 3, BG=2, Modulation="QPSK", rv_id_sequence=(0
     return curves
 
 
+def _snr_vs_a_rate_mixed(path, A_list, r, BG, Q_m, rv_id_sequence, iterations, target_block_errors, target_BLER, EsN0_start, EsN0_delta,
+                         seed, batch, max_points, decoder_kwargs, device_id, simulate):
+    """One rate of plot_SNR_vs_A with all its lengths side by side (mixed=True).  Every length keeps the ladder state the sequential loop
+    keeps for it -- EsN0, found_start, errors, blocks, first_block, its curve_seed, derived as there -- and goes through the same
+    statements in the same order; only the interleaving differs: a round simulates `batch` blocks of EVERY unfinished length at its
+    current Es/N0 in one simulate_point_mixed.  The chains are rebuilt over the remaining lengths when one finishes (at most one
+    rebuild per length).  Payloads and noise are functions of (curve_seed, global block index, attempt) alone, so each length sees the
+    outcomes it sees when simulated alone, and the rows -- written in the order of A once all are in -- are the sequential ones."""
+    states = []
+    for a_len in A_list:                                             # :88
+        s = dict(A=a_len, found_start=False, BLER=1.0, prev_BLER=float("nan"), live=True, skip=False, p=None)   # :90, :95-96
+        s["EsN0"] = float(EsN0_start) - float(EsN0_delta)            # :97
+        s["prev_EsN0"] = s["EsN0"]
+        states.append(s)
+        hEnc = hDec = None
+        try:
+            G = int(round(a_len / r / Q_m) * Q_m)                    # :98
+            if simulate is None:
+                from . import _capi
+                from .nrldpc import NRLDPC
+                hEnc = NRLDPCEncoder(A=a_len, BG=BG, G=G, Q_m=Q_m)                                            # :101
+                hDec = NRLDPCDecoder(A=a_len, BG=BG, G=G, Q_m=Q_m, I_HARQ=1, iterations=iterations, **(decoder_kwargs or {}))  # :102
+                hEnc.validate()
+                s["p"] = NRLDPC(A=a_len, BG=BG, G=G, Q_m=Q_m)
+                s["p"].validate()
+                for layout in (_capi.mix_layout, _capi.mix_tx_layout, _capi.mix_chan_layout):  # what the three plans refuse, on the host
+                    layout([s["p"]], [batch])
+        except UnsupportedParameters:                                # :165-172: skip this (A, R)
+            s["live"], s["skip"] = False, True
+        finally:
+            if hEnc is not None:
+                hEnc.release()
+            if hDec is not None:
+                hDec.release()
+        s["curve_seed"] = (int(seed) * 0x9E3779B97F4A7C15 + a_len) % (1 << 64)  # payload / noise streams of this (seed, A)
+        s["first_block"], s["n_points"] = 0, 0
+
+    def next_point(s):
+        """The head of the SNR loop (:105-115): False when the length is finished."""
+        if not (s["BLER"] > target_BLER and s["n_points"] < max_points):
+            return False
+        s["prev_EsN0"] = s["EsN0"]                                   # :106
+        s["EsN0"] = s["EsN0"] + float(EsN0_delta)                    # :107
+        s["blocks"] = s["errors"] = 0                                # :114-115
+        s["keep_going"], s["bler_now"] = True, 1.0
+        return True
+
+    for s in states:
+        if s["live"]:
+            s["live"] = next_point(s)
+    chains, built_for = None, None
+    try:
+        with open(path, "w") as fid:
+            while any(s["live"] for s in states):
+                act = [s for s in states if s["live"]]
+                if simulate is None and built_for != [s["A"] for s in act]:
+                    from .device_chain import MixedChannel, MixedDecodeChain, MixedEncodeChain
+                    for c in chains or []:
+                        c.close()
+                    ps, cnt = [s["p"] for s in act], [batch] * len(act)
+                    chains = [MixedEncodeChain(ps, cnt, device_id=device_id, one_launch_encode=True)]
+                    chains.append(MixedChannel(ps, cnt, device_id=device_id))
+                    chains.append(MixedDecodeChain(ps, cnt, iterations=iterations, I_HARQ=1, device_id=device_id, **(decoder_kwargs or {})))
+                    built_for = [s["A"] for s in act]
+                if simulate is None:
+                    results = simulate_point_mixed(chains[0], chains[1], chains[2], [s["EsN0"] for s in act], rv_id_sequence,
+                                                   [s["curve_seed"] for s in act], [s["first_block"] for s in act])
+                for k, s in enumerate(act):
+                    if simulate is not None:
+                        try:
+                            outcomes = simulate(s["A"], s["EsN0"], batch, s["first_block"])
+                        except UnsupportedParameters:                # :165-172
+                            s["live"], s["skip"] = False, True
+                            continue
+                    else:
+                        outcomes = results[k]
+                    s["first_block"] += batch
+                    s["found_start"], s["keep_going"], s["errors"], s["blocks"], s["bler_now"] = _count_outcomes(
+                        outcomes, s["found_start"], s["errors"], s["blocks"], s["bler_now"], target_block_errors)
+                    if s["keep_going"] and s["errors"] < target_block_errors:   # :120
+                        continue
+                    s["prev_BLER"] = s["BLER"]                       # :162
+                    s["BLER"] = s["bler_now"]                        # :163
+                    s["n_points"] += 1
+                    s["live"] = next_point(s)
+            rows = []
+            for s in states:
+                if s["skip"]:
+                    continue
+                prev_BLER, BLER, prev_EsN0, EsN0 = s["prev_BLER"], s["BLER"], s["prev_EsN0"], s["EsN0"]
+                # :175, as in plot_SNR_vs_A
+                x0, x1, xt = np.log10(prev_BLER) if prev_BLER == prev_BLER else float("nan"), np.log10(BLER), np.log10(target_BLER)
+                if x0 != x0 or x0 == x1 or not (min(x0, x1) <= xt <= max(x0, x1)):
+                    es = float("nan")
+                else:
+                    es = prev_EsN0 + (EsN0 - prev_EsN0) * (xt - x0) / (x1 - x0)
+                fid.write("%d\t%s\n" % (s["A"], "NaN" if es != es else "%f" % es))      # :186
+                fid.flush()
+                rows.append((s["A"], es))
+    finally:
+        for c in chains or []:
+            c.close()
+    return rows
+
+
 def plot_SNR_vs_A(A=tuple(range(1000, 9000, 1000)), R=1 / 3, BG=1, Modulation="QPSK", rv_id_sequence=(0,), iterations=50,
                   target_block_errors=100, target_BLER=1e-2, EsN0_start=-2.0, EsN0_delta=0.1, seed=0,
                   results_dir="results", batch=256, max_points=400, decoder_kwargs=None, device=False, devices=None,
-                  simulate=None):
+                  simulate=None, mixed=False):
     """The reference's second harness, plot_SNR_vs_A.m:1-194 (same positional parameters and defaults, :38-48; no figure): for every
     coding rate R and information block length A, the Es/N0 at which the BLER crosses target_BLER -- the SNR is stepped up from
     EsN0_start in EsN0_delta steps (:103-108), target_block_errors errors are collected per SNR with the same found_start rule as
@@ -384,17 +537,27 @@ def plot_SNR_vs_A(A=tuple(range(1000, 9000, 1000)), R=1 / 3, BG=1, Modulation="Q
     (:186); parameter sets the objects refuse are skipped (:165-172).  Blocks are simulated in batches, on the host mirror or with
     every stage on the GPU(s) (device=True), exactly as in plot_BLER_vs_SNR.
     simulate: test hook -- a function (A, EsN0, n, first_block) -> per-block outcomes that replaces the simulation.
+    mixed=True (with device=True on one device, or with the hook): all lengths of a rate advance side by side, each on its own Es/N0
+    ladder, every round of `batch` blocks per unfinished length in ONE simulate_point_mixed (_snr_vs_a_rate_mixed); the result file and
+    the return value are those of mixed=False, byte for byte.
     Returns {R: [(A, EsN0 or nan), ...]}."""
     rng = np.random.default_rng(seed)                                # :51
     Q_m = Q_M.get(Modulation)
     if Q_m is None:
         raise UnsupportedParameters("Unsupported modulation")
     A_list, R_list = [int(a) for a in np.atleast_1d(A)], [float(r) for r in np.atleast_1d(R)]
+    if mixed and simulate is None and (not device or len(devices or [0]) != 1):
+        raise UnsupportedParameters("mixed=True runs on one device: it needs device=True with one ordinal, or the simulate hook.")
     os.makedirs(results_dir, exist_ok=True)
     out = {}
     for r in R_list:                                                 # :69
         name = "SNR_vs_A_%s_%s_%s_%s_%s_%s_%s.txt" % (_num2str(target_BLER), _num2str(r), _num2str(BG), Modulation,
                                                       _num2str(iterations), _num2str(target_block_errors), _num2str(seed))  # :80
+        if mixed:
+            out[r] = _snr_vs_a_rate_mixed(os.path.join(results_dir, name), A_list, r, int(BG), Q_m, rv_id_sequence, iterations,
+                                          target_block_errors, target_BLER, EsN0_start, EsN0_delta, seed, batch, max_points,
+                                          decoder_kwargs, int((devices or [0])[0]), simulate)
+            continue
         rows = []
         with open(os.path.join(results_dir, name), "w") as fid:
             for a_len in A_list:                                     # :88
